@@ -8,7 +8,12 @@ A "step" = for the rank's 2 images: upload from pinned host memory + GPU copy-pa
 ahead on a side stream -> forward -> backward (gradient all-reduce over RCCL overlapped) -> fused clip+AdamW+EMA.
 The images, ground truth and packed paste patches sit in pinned HOST buffers when the timed region starts (what the loader's
 pin thread hands over) and go up every step inside it; --inputs-resident stages them in HBM instead; --through-loader feeds the
-same step from the product's real loader (worker processes).  Prints ONE JSON line (rank 0)."""
+same step from the product's real loader (worker processes).  Prints ONE JSON line (rank 0).
+
+A plain run does only what the headline needs: set up, warm up, time --steps steps, print the line (`ms_per_step` = milliseconds
+of one timed step).  --full adds what is measured or checked next to it: the roofline objects (steps re-run behind the timed region
+with per-launch HIP events, cross-checked against the committed profiles), the CPU baseline and, at N > 1, the bucket all-reduce in
+isolation and the weights-identical-across-ranks check.  --dump-outputs DIR writes what the last timed step computed as .npy files."""
 import argparse
 import json
 import os
@@ -32,8 +37,14 @@ def parse():
     p.add_argument("--size", type=int, default=1024)
     p.add_argument("--swin", default="L-22k-384")
     p.add_argument("--batch", type=int, default=2, help="images per GPU (IMS_PER_BATCH 16 / 8 GPUs)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-roofline", action="store_true", help="leave the per-launch HIP events off (A/B of their cost)")
+    p.add_argument("--full", action="store_true",
+                   help="also the measurements and checks the headline does not need: roofline objects, CPU baseline, N > 1 all-reduce "
+                        "in isolation and weights-identical check (--no-roofline / --no-cpu-baseline leave single parts out)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed (losses; fixed seeded samples of the updated "
+                        "weights, their EMA and the gradients) to DIR/<name>.npy, float32")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    p.add_argument("--no-roofline", action="store_true", help="--full without the per-launch HIP events (A/B of their cost)")
     p.add_argument("--roofline-steps", type=int, default=4, help="steps re-run behind the timed region with per-launch HIP events (roofline objects)")
     p.add_argument("--no-copy-paste", action="store_true")
     p.add_argument("--copy-sources", action="store_true", help="development: list the ops of one step that end in device copies / fills (stderr)")
@@ -310,8 +321,25 @@ def cpu_baseline(swin, model, cfg, budget_s=30.0):
                               "what": "oracle/swin.py Swin-%s fwd+bwd alone (round 1's cpu_baseline sample)" % swin}}
 
 
+def dump_outputs(path, losses, total, opt, n_sample=1 << 21):
+    """--dump-outputs: the losses of the last timed step and the same fixed, seeded sample of the flat parameter arena from the
+    updated weights, their EMA and the gradients that step left (float32, 3 x 8 MB at most)."""
+    os.makedirs(path, exist_ok=True)
+    for k, v in losses.items():
+        np.save(os.path.join(path, k + ".npy"), np.asarray(v.detach().float().cpu().numpy(), dtype=np.float32).reshape(-1))
+    np.save(os.path.join(path, "total_loss.npy"), total.detach().float().cpu().numpy().reshape(-1))
+    n = int(opt.arena.p.numel())
+    idx = np.sort(np.random.default_rng(0).choice(n, size=min(n, n_sample), replace=False))
+    idx_t = torch.from_numpy(idx).to(opt.arena.p.device)
+    arrays = {"params_sample": opt.arena.p, "grads_sample": opt.arena.g, "ema_sample": opt.ema}
+    for k, t in arrays.items():
+        if t is not None:
+            np.save(os.path.join(path, k + ".npy"), t.index_select(0, idx_t).float().cpu().numpy())
+
+
 def main():
     a = parse()
+    roofline = a.full and not a.no_roofline
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         relaunch_under_torchrun(a)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -502,6 +530,7 @@ def main():
 
     host = {"feed": 0.0, "forward": 0.0, "backward": 0.0, "optimizer": 0.0}      # host seconds per section (diagnostic)
     pc = time.perf_counter
+    last = {}
 
     def one_step():
         t0 = pc()
@@ -511,6 +540,8 @@ def main():
         opt.zero_grad()
         losses = model(batch)
         total = total_loss(losses)
+        if a.dump_outputs:
+            last["losses"] = losses
         t2 = pc()
         reducer.begin_backward()
         total.backward()
@@ -538,7 +569,7 @@ def main():
         torch.cuda.synchronize()
 
     from divergen_amd.utils import prof
-    prof.enable(not a.no_roofline)            # on from the first step: hipGraph captures (warm-up) record what they replay
+    prof.enable(roofline)                     # on from the first step: hipGraph captures (warm-up) record what they replay
     with EventStorage(0):
         for _ in range(a.warmup):
             one_step()
@@ -546,7 +577,7 @@ def main():
         if a.copy_sources:                    # development: which ops of ONE bench step end in device copies / fills
             _copy_sources(one_step)
             sync()
-        prof.enable(not a.no_roofline)        # restart the tallies: the timed region only
+        prof.enable(roofline)                 # restart the tallies: the timed region only
         prof.pause(True)
         for k_ in host:
             host[k_] = 0.0
@@ -557,13 +588,15 @@ def main():
         t_issue = time.perf_counter() - t0     # host time to ENQUEUE the steps (diagnostic: CPU- vs GPU-bound)
         sync()
         dt = time.perf_counter() - t0
+        if a.dump_outputs and rank == 0:       # what the last timed step computed, before anything else runs a step
+            dump_outputs(a.dump_outputs, last["losses"], total, opt)
         # Per-launch HIP events for the roofline objects.  Since round 6 the Swin blocks are replayed from hipGraphs, and a replayed launch
         # cannot carry events; the two records per heavy launch also cost the host ~10 us each.  The SAME steps (same weights' shapes, same
         # batches in rotation, same kernels and grids) are therefore issued `roofline_steps` more times right behind the timed region with
         # the block groups issued eagerly and the events on; the committed rocprofv3 CSV of the plain command (every dispatch of the timed
         # steps, replayed ones included) cross-checks the family times (`profile` in each object).
         sampled = 0
-        if not a.no_roofline:
+        if roofline:
             from divergen_amd.modeling.backbone import swintransformer as _S
             keep_graphs = _S.GRAPH_BLOCKS
             _S.GRAPH_BLOCKS = False
@@ -576,7 +609,7 @@ def main():
             sync()
             prof.pause(True)
             _S.GRAPH_BLOCKS = keep_graphs
-    stats = prof.read() if not a.no_roofline else {}
+    stats = prof.read() if roofline else {}
     prof.enable(False)
     assert bool(torch.isfinite(total)), "non-finite loss"
     tmax = torch.tensor([dt], device=dev)
@@ -589,7 +622,7 @@ def main():
     # any rank-local contribution that escaped the all-reduce) shows up here as diverged weights: fail loudly.
     in_sync = None
     allreduce = None
-    if world > 1 and exposed:
+    if world > 1 and exposed and a.full:
         # (a) exposed all-reduce time: stream time between the end of backward and the last collective the optimizer waits for,
         #     mean over the timed steps (what overlap did NOT hide); (b) the bucket collective in isolation: 10 all-reduces of one
         #     64 MiB fp32 bucket, bus bandwidth = 2 (N - 1) / N x bytes / time (ring all-reduce: what one xGMI link pair carries)
@@ -609,7 +642,7 @@ def main():
         allreduce = {"exposed_ms_per_step": sum(ex) / max(len(ex), 1), "bucket_bytes": nb * 4, "buckets": len(reducer.buckets),
                      "gradient_bytes_per_step": int(opt.arena.g.numel()) * 4, "bucket_allreduce_ms": t_ar * 1e3,
                      "bucket_bus_gb_per_s": 2.0 * (world - 1) / world * nb * 4 / t_ar / 1e9}
-    if world > 1:
+    if world > 1 and a.full:
         chk = torch.stack([opt.arena.p.double().sum(), opt.arena.p.double().abs().sum()]).cpu()
         gathered = [torch.zeros_like(chk) for _ in range(world)]
         dist.all_gather(gathered, chk.to(dev) if dist.get_backend() == "nccl" else chk)
@@ -621,8 +654,8 @@ def main():
     # (FPN output convs, CenterNet towers) carry no events and are listed next to them with their work.  "roofline" = the
     # family with the largest device time per step.  `profile` repeats the computation from the rocprofv3 CSV committed
     # under profiles/ (every dispatch, graphs included): frac_all_launches = flops_per_step / family_ms_per_step / peak.
-    pmc = _load_json(PROFILE_TAG + "_pmc.json")
-    prof_csv = profile_crosscheck()
+    pmc = _load_json(PROFILE_TAG + "_pmc.json") if roofline else {}
+    prof_csv = profile_crosscheck() if roofline else {}
     objs = []
     nsamp = max(sampled, 1)
     for fam, st in stats.items():
@@ -712,7 +745,7 @@ def main():
             line["weights_identical_across_ranks"] = in_sync
             line["buckets_reduced_during_backward"] = "%d/%d" % (reducer.last_early, len(reducer.buckets))
             line["allreduce"] = allreduce
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(a.swin, model, cfg)
     # RCCL writes its version banner to the C-level stdout, which is block-buffered when redirected and would otherwise be
     # flushed at exit, i.e. AFTER the JSON: every rank drains it (and they meet) before rank 0 prints, so that the JSON

@@ -18,6 +18,7 @@ same augmentation stream.  Polygon rasterisation restates pycocotools' rleFrPoly
 by the reference and absent here: PARITY UNPINNED by reference vectors, pinned by known answers in tests/test_host_data.py).
 """
 import copy
+import gc
 import json
 import logging
 import os
@@ -823,6 +824,10 @@ def build_detection_train_loader(cfg, per_gpu, device, seed):
         prefetch_factor=cfg.DATALOADER.PREFETCH_FACTOR if nw > 0 else None, persistent_workers=nw > 0)
     if nw == 0:
         _worker_init(0, rank_seed, in_worker=False)
+    else:
+        # The workers fork inside BatchAhead (iter(loader)).  Pinned host memory is not mapped into a forked child, so garbage of
+        # this process that still holds pinned tensors is freed here, before the fork, and not by a worker's own collector.
+        gc.collect()
     return BatchAhead(loader, mapper.finish, device)
 
 

@@ -92,3 +92,70 @@ def assembled_oracle_losses(p, images, gts, image_sizes, swin, num_classes, freq
                                      lambda k, gtc, K, Cn, w: det_fed_mask(gtc, K, Cn, w).nonzero().squeeze(1),
                                      mask_weight=mask_weight, stage_labels=stage_labels))
     return losses
+
+
+# ---- the reference's own C++ (oracle/_ref/dgref.so, built by oracle/build.py where the reference's sources are at hand) on the
+# inputs of the tests that compare against it.  Its answers are stored in tests/golden/refcpp.npz (tests/golden/make_golden_refcpp.py):
+# the tests compare against the stored answers everywhere and, where the library is built, check them against it first.
+def rotated_rois(rois):
+    """(batch, x0, y0, x1, y1) -> (batch, cx, cy, w, h, angle 0): the form ROIAlignRotated takes."""
+    cx, cy = (rois[:, 1] + rois[:, 3]) / 2, (rois[:, 2] + rois[:, 4]) / 2
+    w, h = rois[:, 3] - rois[:, 1], rois[:, 4] - rois[:, 2]
+    return torch.stack([rois[:, 0], cx, cy, w, h, torch.zeros_like(w)], 1)
+
+
+def ref_roi_align(ref, feat, rois, go, scale, pooled):
+    """ROIAlignRotated_cpu.cpp at angle 0: (forward output, input gradient of `go`), sampling ratio 0."""
+    rr = rotated_rois(rois)
+    out = ref.roi_align_rotated_forward(feat, rr, scale, pooled, pooled, 0)
+    grad = ref.roi_align_rotated_backward(go, rr, scale, pooled, pooled, *feat.shape, 0)
+    return out, grad
+
+
+def ref_nms(ref, boxes, wh, scores, thr):
+    """nms_rotated_cpu.cpp on axis-aligned (x0, y0, x1, y1) boxes of sizes `wh` at angle 0: the kept indices."""
+    r5 = torch.stack([(boxes[:, 0] + boxes[:, 2]) / 2, (boxes[:, 1] + boxes[:, 3]) / 2, wh[:, 0], wh[:, 1],
+                      torch.zeros(boxes.shape[0])], 1)
+    return ref.nms_rotated(r5, scores, thr)
+
+
+def ref_cocoeval(ref, ev, gt, dets):
+    """cocoeval.cpp (EvaluateImages + Accumulate, what COCOeval_opt calls) on the problem `ev` (a run LVISEval) holds, in the
+    C++ evaluator's input form (D2/evaluation/fast_eval_api.py:55-90).  Returns (precision [T, R, K, A], recall [T, K, A])."""
+    import types
+    import numpy as np
+    from divergen_amd.evaluation import lvis_eval as LE
+    img_ids, cat_ids = ev.img_ids, ev.cat_ids
+    gts = {(i, c): [] for i in img_ids for c in cat_ids}
+    for a in gt["annotations"]:
+        gts[a["image_id"], a["category_id"]].append(a)
+    dts = {(i, c): [] for i in img_ids for c in cat_ids}
+    for k, d in enumerate(dets):
+        e = dict(d)
+        e["id"], e["area"] = k + 1, d["bbox"][2] * d["bbox"][3]
+        dts[d["image_id"], d["category_id"]].append(e)
+    G, D, I = [], [], []
+    for i in img_ids:
+        g_row, d_row, i_row = [], [], []
+        for c in cat_ids:
+            g, d = gts[i, c], dts[i, c]
+            g_row.append([ref.InstanceAnnotation(int(x["id"]), 0.0, float(x["area"]), False, bool(x["ignore"])) for x in g])
+            d_row.append([ref.InstanceAnnotation(int(x["id"]), float(x["score"]), float(x["area"]), False, False) for x in d])
+            ds = sorted(d, key=lambda x: -x["score"])                       # computeIoU: rows in score order (stable), columns as stored
+            i_row.append([[LE.box_iou_xywh(x["bbox"], y["bbox"]) for y in g] for x in ds] if g and ds else [])
+        G.append(g_row), D.append(d_row), I.append(i_row)
+    P = types.SimpleNamespace(recThrs=ev.rec_thrs.tolist(), iouThrs=ev.iou_thrs.tolist(), maxDets=[300], useCats=1,
+                              areaRng=[list(map(float, r)) for r in ev.area_rng], catIds=cat_ids, imgIds=img_ids)
+    E = ref.cocoeval_evaluate_images([list(map(float, r)) for r in ev.area_rng], 300, ev.iou_thrs.tolist(), I, G, D)
+    acc = ref.cocoeval_accumulate(P, E)
+    counts = list(acc["counts"])                                           # T, R, K, A, M
+    prec = np.array(acc["precision"]).reshape(counts)[..., 0]
+    rec = np.array(acc["recall"]).reshape(counts[:1] + counts[2:])[..., 0]
+    return prec, rec
+
+
+def load_refcpp():
+    """oracle/_ref/dgref.so as a module, or None where it is not built (the stored answers stand in)."""
+    from oracle.build import load_ref
+    ref = load_ref()
+    return ref if ref is not None and hasattr(ref, "cocoeval_evaluate_images") else None

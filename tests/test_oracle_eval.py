@@ -1,6 +1,6 @@
 """Evaluation row: the matching / accumulation arithmetic of divergen_amd/evaluation/lvis_eval.py against the
 reference's own C++ evaluator, D2/layers/csrc/cocoeval/cocoeval.cpp (what COCOeval_opt calls, D2/evaluation/fast_eval_api.py:88,109),
-compiled where it lies into oracle/_ref/dgref.so (oracle/build.py).
+compiled where it lies into oracle/_ref/dgref.so (oracle/build.py); its answers are stored in tests/golden/refcpp.npz.
 
 lvis-api itself is not vendored by the reference ("parity unpinned" for the LVIS-only rules: federated filtering, not-exhaustive
 categories, the r / c / f split -- those stay on the hand-worked cases of tests/test_host_eval.py).  What LVISEval shares with
@@ -10,8 +10,6 @@ both algorithms when no ground truth is a crowd and no image holds more than max
 the two must produce THE SAME precision and recall tensors.  IoUs are handed to both sides (box_iou_xywh), so this pins
 matching and accumulation, not the IoU routine (pinned by known answers in test_host_eval.py).
 """
-import types
-
 import numpy as np
 import pytest
 
@@ -56,41 +54,20 @@ def _dataset(seed, n_img=14, n_cat=5, crowd_free=True):
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2])
-def test_lvis_eval_matching_and_accumulation_equal_reference_cocoeval_cpp(seed):
-    from oracle import build as OB
-    ref = OB.load_ref()
-    if ref is None or not hasattr(ref, "cocoeval_evaluate_images"):
-        pytest.skip("oracle/_ref/dgref.so (reference C++ compiled in place) not available")
+def test_lvis_eval_matching_and_accumulation_equal_reference_cocoeval_cpp(seed, golden):
+    from tests._recipes import load_refcpp, ref_cocoeval
     gt, dets = _dataset(seed)
     ev = LE.LVISEval(gt, dets, iou_type="bbox", max_dets=300)
     ev.run()
-    # ---- the same problem in the C++ evaluator's input form (fast_eval_api.py:55-90)
-    img_ids, cat_ids = ev.img_ids, ev.cat_ids
-    gts = {(i, c): [] for i in img_ids for c in cat_ids}
-    for a in gt["annotations"]:
-        gts[a["image_id"], a["category_id"]].append(a)
-    dts = {(i, c): [] for i in img_ids for c in cat_ids}
-    for k, d in enumerate(dets):
-        e = dict(d)
-        e["id"], e["area"] = k + 1, d["bbox"][2] * d["bbox"][3]
-        dts[d["image_id"], d["category_id"]].append(e)
-    G, D, I = [], [], []
-    for i in img_ids:
-        g_row, d_row, i_row = [], [], []
-        for c in cat_ids:
-            g, d = gts[i, c], dts[i, c]
-            g_row.append([ref.InstanceAnnotation(int(x["id"]), 0.0, float(x["area"]), False, bool(x["ignore"])) for x in g])
-            d_row.append([ref.InstanceAnnotation(int(x["id"]), float(x["score"]), float(x["area"]), False, False) for x in d])
-            ds = sorted(d, key=lambda x: -x["score"])                       # computeIoU: rows in score order (stable), columns as stored
-            i_row.append([[LE.box_iou_xywh(x["bbox"], y["bbox"]) for y in g] for x in ds] if g and ds else [])
-        G.append(g_row), D.append(d_row), I.append(i_row)
-    P = types.SimpleNamespace(recThrs=ev.rec_thrs.tolist(), iouThrs=ev.iou_thrs.tolist(), maxDets=[300], useCats=1,
-                              areaRng=[list(map(float, r)) for r in ev.area_rng], catIds=cat_ids, imgIds=img_ids)
-    E = ref.cocoeval_evaluate_images([list(map(float, r)) for r in ev.area_rng], 300, ev.iou_thrs.tolist(), I, G, D)
-    acc = ref.cocoeval_accumulate(P, E)
-    counts = list(acc["counts"])                                           # T, R, K, A, M
-    prec = np.array(acc["precision"]).reshape(counts)[..., 0]
-    rec = np.array(acc["recall"]).reshape(counts[:1] + counts[2:])[..., 0]
+    # ---- the C++ evaluator's answer on the same problem: stored (tests/golden/make_golden_refcpp.py), and where the reference
+    # library is built, recomputed and held to the stored one first
+    z = golden("refcpp")
+    prec, rec = z["cocoeval_precision_%d" % seed], z["cocoeval_recall_%d" % seed]
+    ref = load_refcpp()
+    if ref is not None:
+        live_prec, live_rec = ref_cocoeval(ref, ev, gt, dets)
+        np.testing.assert_array_equal(live_prec, prec)
+        np.testing.assert_array_equal(live_rec, rec)
     assert prec.shape == ev.precision.shape and rec.shape == ev.recall.shape
     assert (prec > -1).sum() > 0.5 * prec.size                              # the comparison is not vacuous
     np.testing.assert_array_equal(prec > -1, ev.precision > -1)

@@ -1,11 +1,9 @@
 """Oracle ROIAlign/NMS/box utilities vs the reference's known-answer tests, the compiled in-tree
 reference sources (oracle/_ref, angle 0) and golden vectors of D2's matcher/sampling/box2box."""
 import numpy as np
-import pytest
 import torch
 
 from oracle import roi as O
-from oracle.build import load_ref
 
 
 def T(a):
@@ -40,33 +38,46 @@ def _rand_rois(g, n, B, H, W):
     return torch.cat([b, xy, xy + wh], 1)
 
 
-def test_roi_align_vs_compiled_reference():
-    """D2T/modeling/test_roi_pooler.py:14-59: ROIAlignV2 == in-tree ROIAlignRotated @ angle 0 (atol 1e-4)."""
-    ref = load_ref()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (no /root/reference and no prebuilt .so)")
+def _roi_align_ref_case():
     g = torch.Generator().manual_seed(5)
     feat = torch.rand(2, 4, 10, 8, generator=g)
     rois = _rand_rois(g, 40, 2, 10 * 4, 8 * 4)
+    go = torch.rand(40, 4, 14, 14, generator=g)
+    return feat, rois, go
+
+
+def test_roi_align_vs_compiled_reference(golden):
+    """D2T/modeling/test_roi_pooler.py:14-59: ROIAlignV2 == in-tree ROIAlignRotated @ angle 0 (atol 1e-4).  The reference's
+    answers are stored (tests/golden/refcpp.npz); where oracle/_ref is built they are recomputed and held to the stored ones."""
+    from tests._recipes import load_refcpp, ref_roi_align
+    feat, rois, go = _roi_align_ref_case()
     scale = 0.25
+    z = golden("refcpp")
+    theirs, gtheirs = T(z["roi_align_fwd_oracle"]), T(z["roi_align_bwd_oracle"])
+    ref = load_refcpp()
+    if ref is not None:
+        live, glive = ref_roi_align(ref, feat, rois, go, scale, 14)
+        assert torch.equal(live, theirs) and torch.equal(glive, gtheirs)
     mine = O.roi_align(feat, rois, scale, 14, 0, True)
-    cx, cy = (rois[:, 1] + rois[:, 3]) / 2, (rois[:, 2] + rois[:, 4]) / 2
-    w, h = rois[:, 3] - rois[:, 1], rois[:, 4] - rois[:, 2]
-    rr = torch.stack([rois[:, 0], cx, cy, w, h, torch.zeros_like(w)], 1)
-    theirs = ref.roi_align_rotated_forward(feat, rr, scale, 14, 14, 0)
     torch.testing.assert_close(mine, theirs, atol=1e-4, rtol=0)
-    go = torch.rand(mine.shape, generator=g)
     gmine = O.roi_align_backward(go, rois, scale, tuple(feat.shape), 0, True)
-    gtheirs = ref.roi_align_rotated_backward(go, rr, scale, 14, 14, 2, 4, 10, 8, 0)
     torch.testing.assert_close(gmine, gtheirs, atol=1e-3, rtol=1e-4)
 
 
-def test_nms_vs_compiled_reference_and_bruteforce():
+def _nms_ref_case():
     g = torch.Generator().manual_seed(9)
     xy = torch.rand(300, 2, generator=g) * 100
     wh = torch.rand(300, 2, generator=g) * 40 + 2
     boxes = torch.cat([xy, xy + wh], 1)
     scores = torch.rand(300, generator=g)
+    return boxes, wh, scores
+
+
+def test_nms_vs_compiled_reference_and_bruteforce(golden):
+    from tests._recipes import load_refcpp, ref_nms
+    boxes, wh, scores = _nms_ref_case()
+    z = golden("refcpp")
+    ref = load_refcpp()
     for thr in (0.3, 0.5, 0.9):
         keep = O.nms(boxes, scores, thr)
         # brute force restatement in torch
@@ -80,14 +91,12 @@ def test_nms_vs_compiled_reference_and_bruteforce():
             bf.append(i)
             dead |= iou[i] > thr
         assert keep.tolist() == bf
-        ref = load_ref()
+        kr = z["nms_keep_oracle_%02d" % round(thr * 10)]
         if ref is not None:
-            cx, cy = (boxes[:, 0] + boxes[:, 2]) / 2, (boxes[:, 1] + boxes[:, 3]) / 2
-            r5 = torch.stack([cx, cy, wh[:, 0], wh[:, 1], torch.zeros(300)], 1)
-            kr = ref.nms_rotated(r5, scores, thr)
-            # polygon-clip IoU may differ from axis-aligned IoU in the last ulp near the threshold
-            a, b = set(keep.tolist()), set(kr.tolist())
-            assert len(a ^ b) <= 2
+            assert ref_nms(ref, boxes, wh, scores, thr).tolist() == kr.tolist()
+        # polygon-clip IoU may differ from axis-aligned IoU in the last ulp near the threshold
+        a, b = set(keep.tolist()), set(kr.tolist())
+        assert len(a ^ b) <= 2
 
 
 def test_batched_nms_per_class():

@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 for r in $(seq ${2:-2}); do
 for v in 0 1; do
-  env $1=$v python bench.py --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+  env $1=$v python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']; o={x['family']:x for x in d['roofline_other']}

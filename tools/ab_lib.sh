@@ -6,7 +6,7 @@ OLD=$GRAFT_REPO_ROOT/$1
 for r in $(seq ${2:-2}); do
 for tag in old new; do
   if [ $tag = old ]; then export DGX_LIB=$OLD; else unset DGX_LIB; fi
-  python bench.py --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+  python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']; o={x['family']:x for x in d['roofline_other']}

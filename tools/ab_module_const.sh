@@ -8,7 +8,7 @@ for v in $A $B; do
 import sys, json, runpy, io, contextlib
 import $MOD as m
 setattr(m, "$NAME", $v)
-sys.argv = ["bench.py", "--steps", "40", "--warmup", "5", "--no-cpu-baseline"]
+sys.argv = ["bench.py", "--full", "--steps", "40", "--warmup", "5", "--no-cpu-baseline"]
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):
     runpy.run_path("bench.py", run_name="__main__")

@@ -17,5 +17,5 @@ rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d /tmp/p_w -o p -
 ff=$(find /tmp/p_f -name "*counter_collection.csv" | head -1)
 fw=$(find /tmp/p_w -name "*counter_collection.csv" | head -1)
 python $R/tools/pmc_summary.py $ff $fw 2 2 $O/r03_pmc.json > $O/pmc_summary.txt 2>&1
-cd $R && python bench.py > $O/r03_bench_line.json 2> $O/bench.err
+cd $R && python bench.py --full > $O/r03_bench_line.json 2> $O/bench.err
 tail -c 1500 $O/r03_bench_line.json

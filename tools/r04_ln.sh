@@ -5,7 +5,7 @@ O=gpurun_out/r4d; mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_kernels.py -x -q -k "layernorm or ln or patch_merge" > $O/test_ln.txt 2>&1; echo "ln tests rc=$?"; tail -3 $O/test_ln.txt
 timeout 1200 python -m pytest tests/test_gpu_parity_modules.py tests/test_gpu_swinL_geometry.py tests/test_gpu_model.py -x -q > $O/test_model.txt 2>&1; echo "model tests rc=$?"; tail -3 $O/test_model.txt
 for r in 1 2; do
-  timeout 600 python bench.py --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+  timeout 600 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']; o={x['family']:x for x in d['roofline_other']}

@@ -19,12 +19,12 @@ fw=$(find /tmp/p_w -name "*counter_collection.csv" | head -1)
 python $R/tools/pmc_summary.py $ff $fw 2 2 $O/r04_pmc.json > $O/pmc_summary.txt 2>&1
 # bench.py cross-checks its event-clock figures against the committed profile of THIS round: put this run's summaries where it reads them
 cp $O/r04_pmc.json $O/r04_profile_meta.json $O/r04_bench_swinL_1024_kernel_stats.csv $R/profiles/
-cd $R && python bench.py > $O/r04_bench_line.json 2> $O/bench.err
+cd $R && python bench.py --full > $O/r04_bench_line.json 2> $O/bench.err
 tail -c 600 $O/r04_bench_line.json
 # what BASELINE.md asks to report beside the headline: the shipped configuration's 896^2 and a Swin-T line (same command, other size / backbone)
-python bench.py --size 896 --steps 60 --no-cpu-baseline > $O/r04_bench_line_896.json 2>> $O/bench.err
-python bench.py --swin T --steps 60 --no-cpu-baseline > $O/r04_bench_line_swinT.json 2>> $O/bench.err
-python bench.py --inputs-resident --steps 60 --no-cpu-baseline > $O/r04_bench_line_inputs_resident.json 2>> $O/bench.err
+python bench.py --full --size 896 --steps 60 --no-cpu-baseline > $O/r04_bench_line_896.json 2>> $O/bench.err
+python bench.py --full --swin T --steps 60 --no-cpu-baseline > $O/r04_bench_line_swinT.json 2>> $O/bench.err
+python bench.py --full --inputs-resident --steps 60 --no-cpu-baseline > $O/r04_bench_line_inputs_resident.json 2>> $O/bench.err
 for f in r04_bench_line_896 r04_bench_line_swinT r04_bench_line_inputs_resident; do python -c "
 import json,sys
 d=json.loads(open('$O/$f.json').read().strip().splitlines()[-1]); print('$f', d['ms_per_step'], d['value'], d['config']['workload'][:60])"; done

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/r5q; mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_gemm.py tests/test_gpu_pins.py -x -q 2>&1 | tail -2
 for r in 1 2; do
-  timeout 600 python bench.py --steps 40 --warmup 5 --no-cpu-baseline $BENCH_EXTRA > $O/bench$r.json 2> $O/err.txt
+  timeout 600 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline $BENCH_EXTRA > $O/bench$r.json 2> $O/err.txt
   python - <<PY
 import json
 d=json.loads(open("$O/bench$r.json").read().strip().splitlines()[-1])

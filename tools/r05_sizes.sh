@@ -1,7 +1,7 @@
 #!/bin/bash
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r5z; mkdir -p $O
 for cfg in "--size 1024" "--size 896" "--swin T --size 1024"; do
-  timeout 600 python bench.py --steps 40 --warmup 5 --no-cpu-baseline $cfg > $O/b.json 2> $O/err.txt
+  timeout 600 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline $cfg > $O/b.json 2> $O/err.txt
   python - <<PY
 import json
 d=json.loads(open("$O/b.json").read().strip().splitlines()[-1])

@@ -2,10 +2,10 @@
 O=gpurun_out/r06_ab; mkdir -p $O
 for rep in 1 2; do
 for size in 1024 896; do
-python bench.py --size $size --steps 60 --warmup 10 --no-cpu-baseline > $O/final_${size}_$rep.json 2>> $O/err.txt
-python bench.py --size $size --steps 60 --warmup 10 --no-cpu-baseline --no-compact > $O/nocompact_${size}_$rep.json 2>> $O/err.txt
-python bench.py --size $size --steps 60 --warmup 10 --no-cpu-baseline --no-block-graphs > $O/noblockgraphs_${size}_$rep.json 2>> $O/err.txt
-python bench.py --size $size --steps 60 --warmup 10 --no-cpu-baseline --no-compact --no-block-graphs > $O/round5form_${size}_$rep.json 2>> $O/err.txt
+python bench.py --full --size $size --steps 60 --warmup 10 --no-cpu-baseline > $O/final_${size}_$rep.json 2>> $O/err.txt
+python bench.py --full --size $size --steps 60 --warmup 10 --no-cpu-baseline --no-compact > $O/nocompact_${size}_$rep.json 2>> $O/err.txt
+python bench.py --full --size $size --steps 60 --warmup 10 --no-cpu-baseline --no-block-graphs > $O/noblockgraphs_${size}_$rep.json 2>> $O/err.txt
+python bench.py --full --size $size --steps 60 --warmup 10 --no-cpu-baseline --no-compact --no-block-graphs > $O/round5form_${size}_$rep.json 2>> $O/err.txt
 done
 done
 python - <<'PY'

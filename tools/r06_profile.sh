@@ -19,12 +19,12 @@ fw=$(find /tmp/p_w -name "*counter_collection.csv" | head -1)
 python $R/tools/pmc_summary.py $ff $fw 2 2 $O/r06_pmc.json > $O/pmc_summary.txt 2>&1
 # bench.py cross-checks its event-clock figures against the committed profile of THIS round: put this run's summaries where it reads them
 cp $O/r06_pmc.json $O/r06_profile_meta.json $O/r06_bench_swinL_1024_kernel_stats.csv $R/profiles/
-cd $R && python bench.py > $O/r06_bench_line.json 2> $O/bench.err
+cd $R && python bench.py --full > $O/r06_bench_line.json 2> $O/bench.err
 tail -c 600 $O/r06_bench_line.json
 # what BASELINE.md asks to report beside the headline: the shipped configuration's 896^2 and a Swin-T line (same command, other size / backbone)
-python bench.py --size 896 --steps 60 --no-cpu-baseline > $O/r06_bench_line_896.json 2>> $O/bench.err
-python bench.py --swin T --steps 60 --no-cpu-baseline > $O/r06_bench_line_swinT.json 2>> $O/bench.err
-python bench.py --inputs-resident --steps 60 --no-cpu-baseline > $O/r06_bench_line_inputs_resident.json 2>> $O/bench.err
+python bench.py --full --size 896 --steps 60 --no-cpu-baseline > $O/r06_bench_line_896.json 2>> $O/bench.err
+python bench.py --full --swin T --steps 60 --no-cpu-baseline > $O/r06_bench_line_swinT.json 2>> $O/bench.err
+python bench.py --full --inputs-resident --steps 60 --no-cpu-baseline > $O/r06_bench_line_inputs_resident.json 2>> $O/bench.err
 for f in r06_bench_line_896 r06_bench_line_swinT r06_bench_line_inputs_resident; do python -c "
 import json,sys
 d=json.loads(open('$O/$f.json').read().strip().splitlines()[-1]); print('$f', d['ms_per_step'], d['value'], d['config']['workload'][:60])"; done
@@ -32,11 +32,11 @@ d=json.loads(open('$O/$f.json').read().strip().splitlines()[-1]); print('$f', d[
 python bench.py --through-loader --steps 60 --warmup 12 --no-cpu-baseline --no-roofline > $O/r06_bench_line_through_loader.json 2>> $O/bench.err
 python bench.py --through-loader --loader-shards --steps 60 --warmup 12 --no-cpu-baseline --no-roofline > $O/r06_bench_line_through_loader_shards.json 2>> $O/bench.err
 python bench.py --through-loader --loader-shards --loader-scale-range 0.1 2.0 --steps 60 --warmup 20 --no-cpu-baseline --no-roofline > $O/r06_bench_line_through_loader_scale_0p1_2.json 2>> $O/bench.err
-python bench.py --gpus 2 --backend gloo --share-device 0 --steps 10 --warmup 4 --no-cpu-baseline --no-roofline > $O/r06_two_rank_gloo_one_gpu.json 2>> $O/bench.err
-python bench.py --gpus 2 --backend gloo --share-device 0 --steps 10 --warmup 4 --no-cpu-baseline --no-roofline --allreduce-dtype bf16 > $O/r06_two_rank_gloo_one_gpu_bf16_wire.json 2>> $O/bench.err
+python bench.py --full --gpus 2 --backend gloo --share-device 0 --steps 10 --warmup 4 --no-cpu-baseline --no-roofline > $O/r06_two_rank_gloo_one_gpu.json 2>> $O/bench.err
+python bench.py --full --gpus 2 --backend gloo --share-device 0 --steps 10 --warmup 4 --no-cpu-baseline --no-roofline --allreduce-dtype bf16 > $O/r06_two_rank_gloo_one_gpu_bf16_wire.json 2>> $O/bench.err
 for f in r06_bench_line_through_loader r06_bench_line_through_loader_shards r06_bench_line_through_loader_scale_0p1_2 r06_two_rank_gloo_one_gpu r06_two_rank_gloo_one_gpu_bf16_wire; do python -c "
 import json,sys
 d=json.loads(open('$O/$f.json').read().strip().splitlines()[-1]); print('$f', d['ms_per_step'], d['value'])"; done
 # the N = 2 code path fed by the real loader (two loaders, 4 workers each, on the one box)
-python bench.py --gpus 2 --backend gloo --share-device 0 --through-loader --loader-shards --workers 4 --steps 10 --warmup 6 --no-cpu-baseline --no-roofline > $O/r06_two_rank_gloo_one_gpu_through_loader.json 2>> $O/bench.err
+python bench.py --full --gpus 2 --backend gloo --share-device 0 --through-loader --loader-shards --workers 4 --steps 10 --warmup 6 --no-cpu-baseline --no-roofline > $O/r06_two_rank_gloo_one_gpu_through_loader.json 2>> $O/bench.err
 tail -c 400 $O/r06_two_rank_gloo_one_gpu_through_loader.json
