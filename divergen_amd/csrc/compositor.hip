@@ -1,5 +1,5 @@
-// Instance copy-paste compositor for gfx950 ('basic' blend), all-integer, bit-exact with the
-// sequential reference (custom_build_copypaste_mapper.py:488-566, :79-92; custom_cp_method.py:5-9).
+// Instance copy-paste compositor for gfx950, bit-exact with the sequential reference
+// (custom_build_copypaste_mapper.py:488-566, :79-92; custom_cp_method.py:5-18: 'basic', 'alpha', 'gaussian' blends).
 //
 // The reference touches the whole (n,H,W) mask stack and the image once PER PASTE.  Here the K
 // pastes are resolved in one sweep: per pixel a K-bit "cover" word says which pastes have alpha>0
@@ -10,6 +10,7 @@
 //   k2 stats        : per object rows, 16 pixels per lane -> runs folded in registers -> LDS histogram over death step -> global atomics
 //   k3 resolve      : statistics staged in LDS, one lane per object: suffixes over the death step, then the replay of the filter
 //   k4 masks        : final masks of all objects, 16 pixels per lane, the cover words read once per pixel group
+// With a non-'basic' blend mode among the pastes, k1 is cp_blend_kernel (same cover words, per-tile blend fold) instead.
 #include "dgx_common.h"
 
 #define CP_MAX_K 31
@@ -245,23 +246,123 @@ __global__ __launch_bounds__(256) void cp_masks_kernel(const uint8_t* __restrict
     }
 }
 
-extern "C" int dgx_copy_paste(uint8_t* image, const uint8_t* masks, const float* boxes0, int n0, int H, int W,
-                              const uint8_t* src_rgba, const int32_t* src_desc, int K, uint8_t* out_masks,
-                              float* out_boxes, uint8_t* out_valid, int32_t* stats, void* stream) {
+// ---- 'alpha' / 'gaussian' blend modes (custom_cp_method.py:5-18): the blend path, taken only when some paste is not 'basic'.
+// One workgroup = a 32 x 8 tile; it writes the tile's cover words (the same bits as cp_cover_blend_kernel) and folds the pastes
+// that reach it, k = 0..K-1 in order, into its pixels, truncating to uint8 after every paste as the reference does.
+//   basic    : D' = S where A > 0 (integer)
+//   alpha    : fp64, a = A / 255.0, D' = trunc(D * (1 - a) + S * a)              (each operation rounded on its own, no FMA)
+//   gaussian : fp32, m = cv2.blur 5x5 of the footprint F = A > 0 over the whole image, BORDER_REFLECT_101 at the image border,
+//              m = (float)((double)count * (1.0 / 25)) from the table below, D' = trunc(fl(D * (1 - m)) + fl(S * m))
+// S is the patch RGB inside the paste rectangle (alpha 0 included) and 0 outside it, so the 2-px halo of 'gaussian' pulls in
+// black outside the rectangle.  A 'gaussian' paste stages the tile's footprint bits + a 2-px halo in LDS (reflect-101 index map)
+// and takes separable 5-tap integer sums.  The library is built with -ffp-contract=off; keep it that way.
+constexpr int CP_TX = 32, CP_TY = 8, CP_HALO = 2;
+constexpr int CP_LX = CP_TX + 2 * CP_HALO, CP_LY = CP_TY + 2 * CP_HALO;
+enum { CP_BASIC = 0, CP_ALPHA = 1, CP_GAUSSIAN = 2 };
+struct CpModes { uint8_t m[CP_MAX_K + 1]; };        // by-value kernel argument: the host decides, nothing is read back
+struct CpBlurTable { float v[26]; };
+constexpr CpBlurTable cp_blur_table() {
+    CpBlurTable t{};
+    for (int c = 0; c <= 25; ++c) t.v[c] = (float)((double)c * (1.0 / 25));
+    return t;
+}
+__constant__ CpBlurTable cp_blur = cp_blur_table();
+
+__device__ __forceinline__ int cp_reflect101(int i, int n) {     // exact for i in [-2, n + 1] (n >= 3); clamped beyond (unused)
+    i = i < 0 ? -i : i;
+    i = i >= n ? 2 * n - 2 - i : i;
+    return min(max(i, 0), n - 1);
+}
+
+__global__ __launch_bounds__(CP_TX * CP_TY) void cp_blend_kernel(uint8_t* __restrict__ image, int H, int W,
+                                                                 const uint8_t* __restrict__ rgba,
+                                                                 const int32_t* __restrict__ desc, int K, CpModes modes,
+                                                                 uint32_t* __restrict__ cover) {
+    __shared__ int32_t d[CP_MAX_K * 5];
+    __shared__ uint8_t fp[CP_LY][CP_LX];           // footprint bits of the tile + halo (reflect-101 coordinates)
+    __shared__ uint8_t hs[CP_LY][CP_TX];           // horizontal 5-tap sums
+    for (int i = threadIdx.x; i < K * 5; i += blockDim.x) d[i] = desc[i];
+    __syncthreads();
+    const int tx0 = blockIdx.x * CP_TX, ty0 = blockIdx.y * CP_TY;
+    const int lx = threadIdx.x % CP_TX, ly = threadIdx.x / CP_TX;
+    const int x = tx0 + lx, y = ty0 + ly;
+    const bool inside = x < W && y < H;
+    const int64_t HW = (int64_t)H * W, p = (int64_t)y * W + x;
+    int r = 0, g = 0, b = 0;
+    bool loaded = false;
+    uint32_t bits = 0;
+    for (int k = 0; k < K; ++k) {                  // block-uniform: pastes whose (expanded) rectangle misses the tile are skipped
+        const int h = d[5 * k + 1], w = d[5 * k + 2], dx = d[5 * k + 3], dy = d[5 * k + 4];
+        const int mode = modes.m[k];
+        const int e = mode == CP_GAUSSIAN ? CP_HALO : 0;
+        if (dx - e >= tx0 + CP_TX || dx + w + e <= tx0 || dy - e >= ty0 + CP_TY || dy + h + e <= ty0) continue;
+        const uint8_t* patch = rgba + d[5 * k];
+        int cnt = 0;
+        if (mode == CP_GAUSSIAN) {
+            for (int i = threadIdx.x; i < CP_LY * CP_LX; i += blockDim.x) {
+                const int gy = cp_reflect101(ty0 - CP_HALO + i / CP_LX, H), gx = cp_reflect101(tx0 - CP_HALO + i % CP_LX, W);
+                const int sx = gx - dx, sy = gy - dy;
+                fp[i / CP_LX][i % CP_LX] = (sx >= 0 && sy >= 0 && sx < w && sy < h) ? (patch[4 * ((int64_t)sy * w + sx) + 3] > 0) : 0;
+            }
+            __syncthreads();
+            for (int i = threadIdx.x; i < CP_LY * CP_TX; i += blockDim.x) {
+                const uint8_t* row = fp[i / CP_TX] + i % CP_TX;
+                hs[i / CP_TX][i % CP_TX] = row[0] + row[1] + row[2] + row[3] + row[4];
+            }
+            __syncthreads();
+            cnt = hs[ly][lx] + hs[ly + 1][lx] + hs[ly + 2][lx] + hs[ly + 3][lx] + hs[ly + 4][lx];
+            __syncthreads();                       // fp / hs are rewritten by the next 'gaussian' paste
+        }
+        if (!inside) continue;
+        const int sx = x - dx, sy = y - dy;
+        const bool inrect = sx >= 0 && sy >= 0 && sx < w && sy < h;
+        const uint8_t* px = inrect ? patch + 4 * ((int64_t)sy * w + sx) : nullptr;
+        const int a = inrect ? px[3] : 0;
+        if (a > 0) bits |= 1u << k;
+        if (mode == CP_GAUSSIAN ? cnt == 0 : a == 0) continue;    // the blend leaves D exactly as it is there
+        if (!loaded) { r = image[p]; g = image[HW + p]; b = image[2 * HW + p]; loaded = true; }
+        const int s0 = inrect ? px[0] : 0, s1 = inrect ? px[1] : 0, s2 = inrect ? px[2] : 0;
+        if (mode == CP_BASIC) {
+            r = s0; g = s1; b = s2;
+        } else if (mode == CP_ALPHA) {
+            const double af = (double)a / 255.0, ia = 1.0 - af;
+            r = (int)((double)r * ia + (double)s0 * af);
+            g = (int)((double)g * ia + (double)s1 * af);
+            b = (int)((double)b * ia + (double)s2 * af);
+        } else {
+            const float m = cp_blur.v[cnt], im = 1.0f - m;
+            r = (int)((float)r * im + (float)s0 * m);
+            g = (int)((float)g * im + (float)s1 * m);
+            b = (int)((float)b * im + (float)s2 * m);
+        }
+    }
+    if (!inside) return;
+    cover[p] = bits;
+    if (loaded) {
+        image[p] = (uint8_t)r;
+        image[HW + p] = (uint8_t)g;
+        image[2 * HW + p] = (uint8_t)b;
+    }
+}
+
+// modes == nullptr: the 'basic' path of every round (cp_cover_blend_kernel); otherwise cp_blend_kernel writes image + cover.
+static int cp_launch(uint8_t* image, const uint8_t* masks, const float* boxes0, int n0, int H, int W, const uint8_t* src_rgba,
+                     const int32_t* src_desc, int K, uint8_t* out_masks, float* out_boxes, uint8_t* out_valid, int32_t* stats,
+                     const CpModes* modes, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (K <= 0 || H <= 0 || W <= 0) return K < 0 ? DGX_ERR_BAD_ARG : DGX_OK;
-    if (K > CP_MAX_K) return DGX_ERR_UNSUPPORTED;
-    if (!image || !src_rgba || !src_desc || !out_masks || !out_boxes || !out_valid || !stats || n0 < 0 ||
-        (n0 > 0 && (!masks || !boxes0)))
-        return DGX_ERR_BAD_ARG;
     // cover words live at the tail of the stats workspace: (n0+K)*(K+1)*5 ints, rounded up to a 16-byte boundary, then H*W words
     const int64_t ns = (int64_t)(n0 + K) * (K + 1) * 5;
     if ((uintptr_t)stats & 15) return DGX_ERR_BAD_ARG;
     uint32_t* cover = reinterpret_cast<uint32_t*>(stats + ((ns + 3) & ~(int64_t)3));
     const int64_t HW = (int64_t)H * W;
-    const int gp = (int)((HW + 255) / 256 < 4096 ? (HW + 255) / 256 : 4096);
     hipLaunchKernelGGL(cp_stats_init_kernel, dim3((int)((ns + 255) / 256)), dim3(256), 0, st, stats, ns);
-    hipLaunchKernelGGL(cp_cover_blend_kernel, dim3(gp), dim3(256), 0, st, image, H, W, src_rgba, src_desc, K, cover);
+    if (modes) {
+        hipLaunchKernelGGL(cp_blend_kernel, dim3((W + CP_TX - 1) / CP_TX, (H + CP_TY - 1) / CP_TY), dim3(CP_TX * CP_TY), 0, st,
+                           image, H, W, src_rgba, src_desc, K, *modes, cover);
+    } else {
+        const int gp = (int)((HW + 255) / 256 < 4096 ? (HW + 255) / 256 : 4096);
+        hipLaunchKernelGGL(cp_cover_blend_kernel, dim3(gp), dim3(256), 0, st, image, H, W, src_rgba, src_desc, K, cover);
+    }
     const int rpb = 32;
     hipLaunchKernelGGL(cp_stats_kernel, dim3(n0 + K, (H + rpb - 1) / rpb), dim3(256), 0, st, masks, cover, src_desc, n0, H, W, K,
                        rpb, stats);
@@ -276,4 +377,42 @@ extern "C" int dgx_copy_paste(uint8_t* image, const uint8_t* masks, const float*
     hipLaunchKernelGGL(cp_masks_kernel, dim3(gx, (n0 + K + opg - 1) / opg), dim3(256), 0, st, masks, cover, n0, H, W, K, opg, out_masks);
     DGX_LAUNCH_CHECK();
     return DGX_OK;
+}
+
+static int cp_check_args(uint8_t* image, const uint8_t* masks, const float* boxes0, int n0, int H, int W, const uint8_t* src_rgba,
+                         const int32_t* src_desc, int K, uint8_t* out_masks, float* out_boxes, uint8_t* out_valid, int32_t* stats) {
+    if (K > CP_MAX_K) return DGX_ERR_UNSUPPORTED;
+    if (!image || !src_rgba || !src_desc || !out_masks || !out_boxes || !out_valid || !stats || n0 < 0 ||
+        (n0 > 0 && (!masks || !boxes0)))
+        return DGX_ERR_BAD_ARG;
+    return DGX_OK;
+}
+
+extern "C" int dgx_copy_paste(uint8_t* image, const uint8_t* masks, const float* boxes0, int n0, int H, int W,
+                              const uint8_t* src_rgba, const int32_t* src_desc, int K, uint8_t* out_masks,
+                              float* out_boxes, uint8_t* out_valid, int32_t* stats, void* stream) {
+    if (K <= 0 || H <= 0 || W <= 0) return K < 0 ? DGX_ERR_BAD_ARG : DGX_OK;
+    const int rc = cp_check_args(image, masks, boxes0, n0, H, W, src_rgba, src_desc, K, out_masks, out_boxes, out_valid, stats);
+    if (rc != DGX_OK) return rc;
+    return cp_launch(image, masks, boxes0, n0, H, W, src_rgba, src_desc, K, out_masks, out_boxes, out_valid, stats, nullptr, stream);
+}
+
+extern "C" int dgx_copy_paste_blend(uint8_t* image, const uint8_t* masks, const float* boxes0, int n0, int H, int W,
+                                    const uint8_t* src_rgba, const int32_t* src_desc, int K, uint8_t* out_masks,
+                                    float* out_boxes, uint8_t* out_valid, int32_t* stats, const uint8_t* modes_host,
+                                    void* stream) {
+    if (K <= 0 || H <= 0 || W <= 0) return K < 0 ? DGX_ERR_BAD_ARG : DGX_OK;
+    const int rc = cp_check_args(image, masks, boxes0, n0, H, W, src_rgba, src_desc, K, out_masks, out_boxes, out_valid, stats);
+    if (rc != DGX_OK) return rc;
+    CpModes modes = {};
+    bool blend = false, gaussian = false;
+    for (int k = 0; modes_host && k < K; ++k) {
+        if (modes_host[k] > CP_GAUSSIAN) return DGX_ERR_BAD_ARG;
+        modes.m[k] = modes_host[k];
+        blend = blend || modes_host[k] != CP_BASIC;
+        gaussian = gaussian || modes_host[k] == CP_GAUSSIAN;
+    }
+    if (gaussian && (H < 3 || W < 3)) return DGX_ERR_UNSUPPORTED;     // reflect-101 needs 3 pixels per side
+    return cp_launch(image, masks, boxes0, n0, H, W, src_rgba, src_desc, K, out_masks, out_boxes, out_valid, stats,
+                     blend ? &modes : nullptr, stream);
 }

@@ -586,6 +586,12 @@ def pack_sample(d):
     out = {k: v for k, v in d.items() if k not in ("image", "instances", "paste_pack")}
     out["blob"], out["blob_layout"] = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.uint8), layout
     out["blob_hw"], out["blob_K"] = tuple(d["image"].shape[-2:]), int(d["paste_pack"]["K"])
+    modes = d["paste_pack"].get("modes")
+    if modes is not None and np.asarray(modes).any():
+        # K blend-mode bytes, read by the host when it launches the compositor (so not in the blob), as a numpy array: it pickles
+        # inline, where a tensor would cost the training thread a shared-memory handle round trip.  All 'basic' (the shipped
+        # configs): nothing is added, the sample crosses the queue exactly as before.
+        out["blob_modes"] = np.ascontiguousarray(modes, dtype=np.uint8)
     extra = {k: v for k, v in d["instances"].get_fields().items() if k not in ("gt_masks", "gt_boxes", "gt_classes")}
     if extra:
         out["blob_extra_fields"] = extra
@@ -616,6 +622,8 @@ def unpack_sample(d, device, ring=None):
         inst.set(k, v.to(device) if hasattr(v, "to") else v)
     out["instances"] = inst
     out["paste_pack"] = {"flat": f["flat"], "desc": f["desc"], "labels": f["labels"], "K": d["blob_K"]}
+    if d.get("blob_modes") is not None:
+        out["paste_pack"]["modes"] = d["blob_modes"]
     return out
 
 
@@ -692,10 +700,12 @@ class _MapDataset(torch.utils.data.Dataset):
         return self.fn(self.dicts[i])
 
 
-def _worker_init(worker_id, base_seed, in_worker=True):
+def _worker_init(worker_id, base_seed, in_worker=True, pool=None):
     seed = (base_seed + worker_id) % (2 ** 31)
     np.random.seed(seed)
     torch.manual_seed(seed)
+    if pool is not None:          # the instance pool's own `random` (blend-mode draws); the process's global `random` stays as it is
+        pool.seed(seed)
     if in_worker:
         torch.set_num_threads(1)      # 16 workers per GPU: one core each
 
@@ -820,10 +830,10 @@ def build_detection_train_loader(cfg, per_gpu, device, seed):
     loader = torch.utils.data.DataLoader(
         _MapDataset(dicts, mapper), sampler=sampler, batch_size=per_gpu, drop_last=True, num_workers=nw,
         collate_fn=_RingCollate(ring) if ring is not None else _identity,
-        worker_init_fn=functools.partial(_worker_init, base_seed=rank_seed), pin_memory=pin_thread,
+        worker_init_fn=functools.partial(_worker_init, base_seed=rank_seed, pool=mapper.inst_pool), pin_memory=pin_thread,
         prefetch_factor=cfg.DATALOADER.PREFETCH_FACTOR if nw > 0 else None, persistent_workers=nw > 0)
     if nw == 0:
-        _worker_init(0, rank_seed, in_worker=False)
+        _worker_init(0, rank_seed, in_worker=False, pool=mapper.inst_pool)
     else:
         # The workers fork inside BatchAhead (iter(loader)).  Pinned host memory is not mapped into a forked child, so garbage of
         # this process that still holds pinned tensors is freed here, before the fork, and not by a worker's own collector.

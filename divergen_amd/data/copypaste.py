@@ -1,24 +1,44 @@
 """DiverGen copy-paste data path with the GPU compositor.
 
 Host-side mirror of InstPool (DG/divergen/data/custom_build_copypaste_mapper.py:94-566) for the shipped
-configuration (INST_POOL_FORMAT 'RGBA', INST_POOL_SAMPLE_TYPE 'cas_random', CP_METHOD ['basic'],
-USE_COPY_METHOD 'syn_copy'): class-balanced sampling of generated instances, size prior (Gaussian
+configuration (INST_POOL_FORMAT 'RGBA', INST_POOL_SAMPLE_TYPE 'cas_random', USE_COPY_METHOD 'syn_copy') with the blend modes
+'basic', 'alpha' and 'gaussian' of INPUT.CP_METHOD (custom_cp_method.py:5-18): class-balanced sampling of generated instances, size prior (Gaussian
 relative-area prior for LVIS classes with statistics, U(RANDOM_SCALE_MIN, MAX) of the source size for
 the rest), random placement.  Two halves:
   InstPool.prepare    numpy / PIL only, the reference's np.random call order (pinned on tests/golden/pool_draws.npz, draws of
                       the reference's own InstPool); runs in the DATALOADER.NUM_WORKERS loader processes and returns the K
-                      patches packed into one flat buffer + descriptors (CPU tensors)
-  InstPool.composite  training process: upload + ONE call into libdgx (dgx_copy_paste) for the pixels -- image blend, mask
-                      occlusion updates, box recomputation and the occlusion filter of `_copy_paste`, all pastes at once."""
+                      patches packed into one flat buffer + descriptors (CPU tensors) + one blend mode per paste, drawn like
+                      blend_image's `random.sample(cp_method, 1)[0]` from the pool's OWN random.Random (seeded by the loader's
+                      _worker_init with the worker's seed, as D2's seed_all_rng seeds `random`; the process's global `random`
+                      and the np.random stream are not touched)
+  InstPool.composite  training process: upload + ONE call into libdgx (dgx_copy_paste, or dgx_copy_paste_blend when a paste is
+                      not 'basic') for the pixels -- image blend, mask occlusion updates, box recomputation and the occlusion
+                      filter of `_copy_paste`, all pastes at once.
+'possion' (Poisson blending, a sparse solve over all H*W pixels per channel per paste) is not built: from_config refuses it."""
 import json
 import os
+import random
 from collections import defaultdict
 
 import numpy as np
 import torch
 
-from ..layers.copy_paste import PackedPastes, copy_paste
+from ..layers.copy_paste import BLEND_MODES, PackedPastes, copy_paste
 from ..structures import BitMasks, Boxes, Instances
+
+
+def check_cp_method(cp_method):
+    """INPUT.CP_METHOD -> list of mode names; every name must be a built blend mode (layers.copy_paste.BLEND_MODES)."""
+    names = [cp_method] if isinstance(cp_method, str) else list(cp_method)
+    if not names:
+        raise ValueError("INPUT.CP_METHOD is empty: name at least one of %s" % sorted(BLEND_MODES))
+    for n in names:
+        if n == "possion":
+            raise NotImplementedError("INPUT.CP_METHOD 'possion' is not built: the reference solves a sparse system over all H*W "
+                                      "pixels per channel per paste (spsolve), which needs a GPU solver of its own")
+        if n not in BLEND_MODES:
+            raise NotImplementedError("INPUT.CP_METHOD '%s' is not a blend mode of this build (%s)" % (n, ", ".join(sorted(BLEND_MODES))))
+    return names
 
 
 def largest_connected_component(mask):
@@ -35,7 +55,7 @@ class InstPool:
     def __init__(self, pool_json, train_size, area_stats_json=None, max_samples=20, random_scale=False,
                  random_scale_min=0.1, random_scale_max=2.0, random_scale_min_size=5, use_largest_part=True,
                  scale_min=10, scale_max=0.5, shape_jitter=0.2, mask_threshold=128,
-                 instance_filter_min=0.01, instance_filter_max=1.0, loader=None):
+                 instance_filter_min=0.01, instance_filter_max=1.0, loader=None, cp_method=("basic",)):
         pool = json.load(open(pool_json)) if isinstance(pool_json, str) else pool_json
         self.per_cat_pool = defaultdict(list)
         self.dataset, self.data_to_cat = [], {}
@@ -53,12 +73,19 @@ class InstPool:
         self.shape_jitter, self.mask_threshold = shape_jitter, mask_threshold
         self.filter_min, self.filter_max = instance_filter_min, instance_filter_max
         self.loader = loader or self._pil_loader
+        self.cp_method = check_cp_method(cp_method)
+        self.rng = random.Random()        # blend-mode draws only (seed: the loader's _worker_init); never the global `random`
+
+    def seed(self, seed):
+        """What D2's seed_all_rng does to `random` in a loader worker, done to the pool's own generator."""
+        self.rng.seed(seed)
 
     @classmethod
     def from_config(cls, cfg):
         """The constructor call of CopyPasteMapper.from_config (mapper.py:726-745) for INST_POOL_FORMAT 'RGBA', including
         the category filter of InstPool.__init__ (:115-133: keep pool categories whose LVIS frequency is in INST_POOL_FREQ).
-        INPUT.INST_POOL_SHARDS (this build's key) switches the per-sample decode to the shard store."""
+        INPUT.INST_POOL_SHARDS (this build's key) switches the per-sample decode to the shard store.  INPUT.CP_METHOD is checked
+        here: 'possion' and unknown names raise NotImplementedError."""
         with open(cfg.INPUT.INST_POOL_PATH) as f:
             pool = json.load(f)
         freq_path = cfg.MODEL.ROI_BOX_HEAD.CAT_FREQ_PATH
@@ -74,7 +101,8 @@ class InstPool:
         return cls(pool, cfg.INPUT.TRAIN_SIZE, area_stats_json=cfg.INPUT.MEAN_STD2_PATH,
                    max_samples=cfg.INPUT.INST_POOL_MAX_SAMPLES, random_scale=cfg.INPUT.RANDOM_SCALE,
                    random_scale_min=cfg.INPUT.RANDOM_SCALE_MIN, random_scale_max=cfg.INPUT.RANDOM_SCALE_MAX,
-                   random_scale_min_size=cfg.INPUT.RANDOM_SCALE_MIN_SIZE, use_largest_part=cfg.USE_LARGEST_PART, loader=loader)
+                   random_scale_min_size=cfg.INPUT.RANDOM_SCALE_MIN_SIZE, use_largest_part=cfg.USE_LARGEST_PART, loader=loader,
+                   cp_method=cfg.INPUT.CP_METHOD)
 
     @staticmethod
     def _pil_loader(path):
@@ -178,23 +206,34 @@ class InstPool:
             names.append(key)
         return pastes, names
 
+    def draw_modes(self, K):
+        """The blend mode of each of K surviving pastes, in paste order: blend_image's `random.sample(cp_method, 1)[0]`
+        (custom_cp_method.py:6, one call per _copy_paste, even for a one-element list) on the pool's own generator.
+        The sequence equals blend_image's own draws from the same seed.  In the reference, `random` also feeds the
+        albumentations Compose that every loaded patch passes through first (mapper.py:496, `cumstom_augmentations`, empty
+        unless INPUT.COLOR_AUG): whether that draws from the global `random`, and how often, depends on the albumentations
+        version, which the reference does not pin.  Those draws are not replayed here; the per-paste distribution is the same."""
+        return np.array([BLEND_MODES[self.rng.sample(self.cp_method, 1)[0]] for _ in range(K)], dtype=np.uint8)
+
     def prepare(self, data):
         """Loader-worker half of get_mix_result: draw + decode + clean + resize + flip + place + pack.  Adds to the mapped sample
-        `paste_pack` = dict(flat uint8, desc int32 (K,5), labels int64 (K), K) -- CPU tensors, the compositor's input form --
-        and `paste_labels` / `paste_filename_list` (BSGAL's selection reads these).  No device, no libdgx."""
+        `paste_pack` = dict(flat uint8, desc int32 (K,5), labels int64 (K), K) -- CPU tensors, the compositor's input form -- plus
+        `modes`, the K blend-mode bytes as a numpy uint8 array (host data, never uploaded; data/build.py hands it over outside the
+        blob, and only when some paste is not 'basic') -- and `paste_labels` / `paste_filename_list` (BSGAL's selection reads these).  No device, no libdgx."""
         from ..layers.copy_paste import pack_pastes_host
         H, W = data["image"].shape[-2:]
         pastes, names = self.draw((H, W))
         flat, desc, labels = pack_pastes_host(pastes)
         data = dict(data)
-        data["paste_pack"] = {"flat": flat, "desc": desc, "labels": labels, "K": len(pastes)}
+        data["paste_pack"] = {"flat": flat, "desc": desc, "labels": labels, "modes": self.draw_modes(len(pastes)),
+                              "K": len(pastes)}
         data["paste_labels"], data["paste_filename_list"] = [p[3] for p in pastes], names
         return data
 
     @staticmethod
     def composite(data, device):
         """Training-process half: the prepared sample's tensors go to `device` (asynchronously when they are pinned) and ONE
-        dgx_copy_paste call on the CURRENT stream blends all K patches, updates masks / boxes and drops covered objects.  The
+        dgx_copy_paste(_blend) call on the CURRENT stream blends all K patches, updates masks / boxes and drops covered objects.  The
         caller chooses the stream (data/build.py: a side stream, one batch ahead of the training stream)."""
         pk = data["paste_pack"]
         inst = data["instances"]
@@ -202,7 +241,7 @@ class InstPool:
         up = lambda t: t.to(device, non_blocking=True)     # noqa: E731
         image, gm = up(data["image"]), up(inst.gt_masks.tensor.view(torch.uint8))
         gb, gc = up(inst.gt_boxes.tensor), up(inst.gt_classes)
-        packed = PackedPastes(up(pk["flat"]), up(pk["desc"]), up(pk["labels"]), int(pk["K"]))
+        packed = PackedPastes(up(pk["flat"]), up(pk["desc"]), up(pk["labels"]), int(pk["K"]), pk.get("modes"))      # modes stay on the host
         out = copy_paste(image, gm, gb, gc, packed, lazy_masks=True)
         ni = Instances((H, W))
         ni.gt_boxes, ni.gt_classes = Boxes(out["boxes"]), out["labels"]

@@ -7,12 +7,40 @@ from .. import _lib as L
 from ..utils.h2d import upload_i32
 
 
+BLEND_MODES = {"basic": 0, "alpha": 1, "gaussian": 2}      # the mode bytes of dgx_copy_paste_blend (include/divergen_hip.h)
+
+
+def host_modes(modes, K):
+    """modes (None | sequence of names or codes | uint8 array / CPU tensor) -> uint8 numpy (K,) in host memory, or None when every
+    paste is 'basic' (then the compositor launches exactly the kernels of dgx_copy_paste)."""
+    if modes is None:
+        return None
+    if isinstance(modes, torch.Tensor):
+        modes = modes.cpu().numpy()
+    if isinstance(modes, np.ndarray):
+        if modes.dtype.kind not in "iu":
+            raise ValueError("copy_paste: blend modes as an array must be integer codes, got dtype %s" % modes.dtype)
+        vals = modes.reshape(-1).tolist()
+    else:
+        vals = list(modes)            # element by element: a mixed list of names and codes keeps its codes
+    for v in vals:
+        if isinstance(v, str) and v not in BLEND_MODES:
+            raise ValueError("copy_paste: unknown blend mode '%s' (%s)" % (v, ", ".join(sorted(BLEND_MODES))))
+    m = np.array([BLEND_MODES[v] if isinstance(v, str) else int(v) for v in vals], dtype=np.int64)
+    if m.shape[0] != K:
+        raise ValueError("copy_paste: %d blend modes for %d pastes" % (m.shape[0], K))
+    if ((m < 0) | (m > 2)).any():
+        raise ValueError("copy_paste: blend mode codes are 0 (basic), 1 (alpha), 2 (gaussian); got %s" % m.tolist())
+    return m.astype(np.uint8) if m.any() else None
+
+
 class PackedPastes:
     """The K paste patches of one image as the kernel takes them: ONE flat uint8 buffer (each RGBA patch padded to 4 bytes) + the
-    (K, 5) int32 descriptors (byte offset, h, w, x0, y0) + the K labels, all on the device."""
+    (K, 5) int32 descriptors (byte offset, h, w, x0, y0) + the K labels, all on the device; `modes`: the K blend-mode bytes
+    (BLEND_MODES) in HOST memory, None = all 'basic'."""
 
-    def __init__(self, flat, desc, labels, K):
-        self.flat, self.desc, self.labels, self.K = flat, desc, labels, K
+    def __init__(self, flat, desc, labels, K, modes=None):
+        self.flat, self.desc, self.labels, self.K, self.modes = flat, desc, labels, K, modes
 
     def __len__(self):
         return self.K
@@ -36,8 +64,8 @@ def pack_pastes_host(pastes):
     return torch.from_numpy(host), torch.from_numpy(np.asarray(desc, dtype=np.int32).reshape(-1, 5)), torch.from_numpy(labels)
 
 
-def pack_pastes(pastes, device):
-    """list of (rgba uint8 (h, w, 4) numpy | tensor, x0, y0, label) -> PackedPastes.  Host arrays (the loader's case: patches come
+def pack_pastes(pastes, device, modes=None):
+    """modes: K blend modes (names or BLEND_MODES codes), None = all 'basic'.  list of (rgba uint8 (h, w, 4) numpy | tensor, x0, y0, label) -> PackedPastes.  Host arrays (the loader's case: patches come
     out of the instance pool in host memory) are laid out in one host buffer and go up in ONE copy; patches that already live on
     the device are gathered with one concatenation.  Round 2 concatenated 2 K device chunks per image inside every step, which
     torch executes as one hipMemcpyAsync per chunk: 38 blit launches of ~10 us per image (0.8 ms per step on the loader stream)."""
@@ -56,23 +84,25 @@ def pack_pastes(pastes, device):
         flat = torch.cat(chunks)
         desc_t = upload_i32(desc, device).view(-1, 5)
         labels = upload_i32([int(np.asarray(p[3]).reshape(-1)[0]) for p in pastes], device).long()
-        return PackedPastes(flat, desc_t, labels, K)
+        return PackedPastes(flat, desc_t, labels, K, modes)
     flat, desc, labels = pack_pastes_host(pastes)
     if torch.device(device).type != "cuda":
-        return PackedPastes(flat, desc, labels, K)
+        return PackedPastes(flat, desc, labels, K, modes)
     flat = flat.pin_memory().to(device, non_blocking=True)
     desc_t = upload_i32(desc.numpy(), device).view(-1, 5) if K else torch.zeros(0, 5, dtype=torch.int32, device=device)
     labels = upload_i32(labels.numpy(), device).long() if K else torch.zeros(0, dtype=torch.int64, device=device)
-    return PackedPastes(flat, desc_t, labels, K)
+    return PackedPastes(flat, desc_t, labels, K, modes)
 
 
-def copy_paste(image, masks, boxes, labels, pastes, lazy_masks=False):
+def copy_paste(image, masks, boxes, labels, pastes, lazy_masks=False, modes=None):
     """image uint8 (3,H,W), masks uint8 (n,H,W), boxes f32 (n,4), labels i64 (n) -- GPU tensors.
     pastes: list of (rgba uint8 numpy/tensor (h,w,4), x0, y0, label) applied in order, or a PackedPastes (pack_pastes).
     Returns dict(image, masks, boxes, labels, source) exactly like the sequential reference.  Mask bytes pass through (0/1 in,
     0/1 out).  lazy_masks: `masks` holds ALL n + K objects' rows and `keep` (i64) the rows of the surviving ones, in order --
     what structures.BitMasks(masks, index=keep) takes: the full-resolution rows of the survivors are then never gathered
-    (the only consumer, crop_and_resize, reads a few rows through the index)."""
+    (the only consumer, crop_and_resize, reads a few rows through the index).
+    modes: the K blend modes (names or BLEND_MODES codes, host memory); None takes the PackedPastes' own (None there = all 'basic').
+    All 'basic' calls dgx_copy_paste; any other mix dgx_copy_paste_blend.  Masks / boxes / labels / source do not depend on them."""
     K = len(pastes)
     dev = image.device
     n0, H, W = masks.shape[0], image.shape[1], image.shape[2]
@@ -82,6 +112,7 @@ def copy_paste(image, masks, boxes, labels, pastes, lazy_masks=False):
             out["keep"] = torch.arange(n0, dtype=torch.int64, device=dev)
         return out
     pk = pastes if isinstance(pastes, PackedPastes) else pack_pastes(pastes, dev)
+    hm = host_modes(modes if modes is not None else pk.modes, K)
     flat, desc_t = pk.flat, pk.desc
     image = image.contiguous().clone()
     masks = masks.contiguous()
@@ -91,9 +122,14 @@ def copy_paste(image, masks, boxes, labels, pastes, lazy_masks=False):
     out_boxes = torch.empty(nobj, 4, dtype=torch.float32, device=dev)
     out_valid = torch.empty(nobj, dtype=torch.uint8, device=dev)
     stats = torch.empty(nobj * (K + 1) * 5 + 3 + H * W, dtype=torch.int32, device=dev)
-    L.check(L.lib().dgx_copy_paste(L.ptr(image), L.ptr(masks) if n0 else None, L.ptr(boxes0) if n0 else None, n0, H, W,
-                                   L.ptr(flat), L.ptr(desc_t), K, L.ptr(out_masks), L.ptr(out_boxes), L.ptr(out_valid),
-                                   L.ptr(stats), L.stream()), "dgx_copy_paste")
+    if hm is None:
+        L.check(L.lib().dgx_copy_paste(L.ptr(image), L.ptr(masks) if n0 else None, L.ptr(boxes0) if n0 else None, n0, H, W,
+                                       L.ptr(flat), L.ptr(desc_t), K, L.ptr(out_masks), L.ptr(out_boxes), L.ptr(out_valid),
+                                       L.ptr(stats), L.stream()), "dgx_copy_paste")
+    else:
+        L.check(L.lib().dgx_copy_paste_blend(L.ptr(image), L.ptr(masks) if n0 else None, L.ptr(boxes0) if n0 else None, n0, H, W,
+                                             L.ptr(flat), L.ptr(desc_t), K, L.ptr(out_masks), L.ptr(out_boxes), L.ptr(out_valid),
+                                             L.ptr(stats), hm.ctypes.data, L.stream()), "dgx_copy_paste_blend")
     keep = out_valid.nonzero().squeeze(1)          # ONE compaction (and one device->host count) for the four per-object tensors
     all_labels = torch.cat([labels.to(torch.int64), pk.labels])
     source = torch.cat([torch.zeros(n0, dtype=torch.int64, device=dev), torch.ones(K, dtype=torch.int64, device=dev)])

@@ -293,7 +293,7 @@ int dgx_centernet_label_inds(const float* gt_boxes, const int32_t* gt_offsets, i
                              const int32_t* strides, const float* soi, int L, int64_t* ind, uint8_t* cared, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Instance copy-paste compositor ('basic' blend).  Replaces the per-paste numpy passes of
+ * Instance copy-paste compositor ('basic' blend; other modes: dgx_copy_paste_blend below).  Replaces the per-paste numpy passes of
  * InstPool._cat_a_new_image / _copy_paste / get_bboxes / blend_image:
  * DG/divergen/data/custom_build_copypaste_mapper.py:488-566, :79-92;
  * DG/divergen/data/transforms/custom_cp_method.py:5-9.
@@ -312,6 +312,23 @@ int dgx_centernet_label_inds(const float* gt_boxes, const int32_t* gt_offsets, i
 int dgx_copy_paste(uint8_t* image, const uint8_t* masks, const float* boxes0, int n0, int H, int W,
                    const uint8_t* src_rgba, const int32_t* src_desc, int K, uint8_t* out_masks,
                    float* out_boxes, uint8_t* out_valid, int32_t* stats, void* stream);
+/* dgx_copy_paste with a blend mode per paste (INPUT.CP_METHOD; DG/divergen/data/transforms/custom_cp_method.py:5-18).
+ * modes_host: K bytes in HOST memory, 0 = 'basic', 1 = 'alpha', 2 = 'gaussian'; NULL = all 'basic'.  When every paste is 'basic'
+ * the call is dgx_copy_paste (the same kernels); otherwise the cover words are those of dgx_copy_paste and the image is folded
+ * per pixel, paste k = 0..K-1 in order, truncated to uint8 after every paste (`.astype(dst_img.dtype)`).  With A_k the placed
+ * alpha of paste k (0 outside its rectangle), F_k = A_k > 0 and S_k the placed RGB (the patch RGB inside the rectangle, alpha-0
+ * pixels included; 0 outside it):
+ *   basic    : D' = S_k where F_k, else D
+ *   alpha    : fp64, a = A_k / 255.0;  D' = trunc(D * (1.0 - a) + S_k * a), every operation rounded on its own (no FMA);
+ *              D' = D where A_k == 0
+ *   gaussian : fp32, m = cv2.blur(F_k, (5, 5)): 5x5 box, centre anchor, BORDER_REFLECT_101 at the IMAGE border, over the full
+ *              H x W mask; m = (float)((double)count * (1.0 / 25));  D' = trunc(fl(fl(D * (1 - m)) + fl(S_k * m))).  The blend
+ *              reaches 2 px outside the footprint (background RGB inside the rectangle, black outside it), as the reference's.
+ * Masks, boxes and out_valid do not depend on the modes.  A mode byte above 2 -> DGX_ERR_BAD_ARG; a 'gaussian' paste on an
+ * image with H < 3 or W < 3 -> DGX_ERR_UNSUPPORTED (reflect-101 is not defined there).  'possion' is not built. */
+int dgx_copy_paste_blend(uint8_t* image, const uint8_t* masks, const float* boxes0, int n0, int H, int W,
+                         const uint8_t* src_rgba, const int32_t* src_desc, int K, uint8_t* out_masks,
+                         float* out_boxes, uint8_t* out_valid, int32_t* stats, const uint8_t* modes_host, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Fused parameter update over a flat arena: per-element gradient value clip, AdamW, EMA lerp of
