@@ -174,7 +174,8 @@ GRAPH_GROUP = 6
 # 72 T C^2 FLOP (12 C^2 per token forward, x 3) at ~0.7 PFLOP/s.  Swin-L at 1024^2 (348 GFLOP per block in every stage) keeps the GPU
 # busy for as long as the host needs to issue it, and there the replayed groups were SLOWER in a same-box A/B (26.8 -> 28.0 ms/step,
 # profiles/r06_ab_compact_blockgraphs.txt: the replay's node-to-node gaps and the lost first-writer protocol -- a replayed group
-# accumulates into zero-filled segments); Swin-T at 1024^2 (87 GFLOP per block) went 14.4 -> 12.3 ms/step.  Groups are replayed when a
+# accumulates, so its segments are zero-filled by zero_grad, or zeroed before the replay where the lazy zero_grad left them to an eager
+# step's first writer: solver.FlatArena.claim_replay); Swin-T at 1024^2 (87 GFLOP per block) went 14.4 -> 12.3 ms/step.  Groups are replayed when a
 # block is below this much work, issued eagerly above it.
 GRAPH_BLOCKS_MAX_GFLOP = 150.0
 

@@ -224,6 +224,8 @@ class FlatArena:
     # zero_grad calls; `written[i]` is the generation in which parameter i was last written directly; `direct` the parameters
     # learned (from the previous step) to be written that way; whatever of them has NOT been written when the gradients are
     # consumed (finish_grads: optimizer step, reducer flush) is zeroed then, so a skipped layer can never leave a stale gradient.
+    # A replayed hipGraph runs no Python between its launches: the segment claims its parameters before the replay (claim_replay),
+    # and a capture leaves the bookkeeping and the gradients as it found them (grad_state / restore_grad_state).
     gen = 0
 
     def _direct_state(self):
@@ -252,6 +254,35 @@ class FlatArena:
             self.written[i] = self.gen
             self._lazy_pending.discard(i)
         return first
+
+    def claim_replay(self, params):
+        """A replayed hipGraph (utils/graphs.GraphedSegment) is about to write the gradient segments of `params` with its captured,
+        ACCUMULATING launches (beta = 1: a captured launch cannot ask whether it is the first writer) and runs no Python that could
+        claim them.  The segments the lazy zero_grad left to their first writer are zeroed now; none of them stays `direct` (the next
+        zero_grad fills them like everything else), and all count as written in this generation, so a later eager launch into them
+        in the same pass accumulates.  Nothing pending (every replay of a steady run): no device work."""
+        self._direct_state()
+        for q in params:
+            i = q._dgx_arena_slot[1]
+            if i in self._lazy_pending:
+                self.g[self.offsets[i]:self.offsets[i] + self.sizes[i]].zero_()
+                self._lazy_pending.discard(i)
+            self.direct.discard(i)
+            self.written[i] = self.gen
+
+    def grad_state(self, params):
+        """Snapshot of the gradient segments of `params` and of their first-writer bookkeeping (restore_grad_state puts it back):
+        taken around a hipGraph capture, whose warm-up passes write and claim those segments outside any training step."""
+        self._direct_state()
+        return [(i, self.written[i], i in self.direct, i in self._lazy_pending, self.g[self.offsets[i]:self.offsets[i] + self.sizes[i]].clone())
+                for i in sorted({q._dgx_arena_slot[1] for q in params})]
+
+    def restore_grad_state(self, state):
+        for i, written, direct, pending, g in state:
+            self.g[self.offsets[i]:self.offsets[i] + self.sizes[i]].copy_(g)
+            self.written[i] = written
+            (self.direct.add if direct else self.direct.discard)(i)
+            (self._lazy_pending.add if pending else self._lazy_pending.discard)(i)
 
     def zero_grad(self, lazy=False):
         """lazy: skip the segments of the parameters that were written directly in the previous step (the training loop's

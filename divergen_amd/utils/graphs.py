@@ -75,6 +75,31 @@ class GraphedSegment:
     def _key(inputs, tag=None):
         return tuple((tuple(t.shape), t.dtype, t.requires_grad, tuple(t.stride())) for t in inputs) + (torch.is_autocast_enabled(), tag)
 
+    def _grad_params(self):
+        params = self.__dict__.get("_params")
+        if params is None:
+            params = self.__dict__["_params"] = tuple(p for p in self.module.parameters() if p.requires_grad)
+        return params
+
+    def _arena_params(self):
+        """[(FlatArena, its parameters among the segment's)] -- a parameter group's handle stands for every member (one GEMM writes
+        the group's rows).  Empty until the arena's first-writer bookkeeping exists (its first zero_grad): nothing is claimed before."""
+        groups = self.__dict__.get("_arena_groups")
+        if groups is None:
+            by, complete = {}, True
+            for p in self._grad_params():
+                for q in getattr(p, "_dgx_group_members", None) or (p,):
+                    slot = getattr(q, "_dgx_arena_slot", None)
+                    if slot is None:
+                        complete = False
+                        continue
+                    ps = by.setdefault(id(slot[0]), (slot[0], {}))[1]
+                    ps[id(q)] = q
+            groups = [(a, tuple(ps.values())) for a, ps in by.values()]
+            if complete:
+                self.__dict__["_arena_groups"] = groups
+        return groups
+
     def usable(self, inputs, tag=None):
         """True when this call replays (or now captures) a graph; False = run the segment eagerly.  `tag`: whatever else the
         segment's launch shapes depend on (the (H, W) of a token grid that arrives flattened)."""
@@ -111,6 +136,12 @@ class GraphedSegment:
             if warn is not None:
                 warn(False)
             from .. import _lib as L
+            # the warm-up runs real backward passes (on uninitialised output gradients) that write and claim the segment's gradient
+            # segments; none of that belongs to a training step: the capture leaves gradients and first-writer bookkeeping as it
+            # found them -- exact also when part of this step's backward has already run
+            saved = [(a, a.grad_state(ps)) for a, ps in self._arena_params()]
+            loose = [(p.grad, p.grad.clone()) for p in self._grad_params()
+                     if p.grad is not None and getattr(p, "_dgx_arena_slot", None) is None]     # (no bookkeeping yet: before the first zero_grad)
             width = L.reserved_cus()
             if CAPTURE_RESERVED_CUS != width:
                 L.set_reserved_cus(CAPTURE_RESERVED_CUS)
@@ -127,21 +158,21 @@ class GraphedSegment:
                     L.set_reserved_cus(width)
                 if warn is not None:
                     warn(True)
+                for a, state in saved:
+                    a.restore_grad_state(state)
+                for g, g0 in loose:
+                    g.copy_(g0)
             if before is not None:      # heavy launches recorded into the two graphs (forward + backward): credited per replay
                 after = prof.captured_snapshot()
                 self._work[key] = {k: tuple(x - y for x, y in zip(after[k], before[k])) for k in after}
-            # the capture warm-up ran real backward passes whose in-place gradient writes landed in the arena;
-            # this step's backward has not started yet, so clearing them is exact
-            for p in self.module.parameters():
-                if p.grad is not None:
-                    p.grad.zero_()
             self._fns[key] = fn
+        # the replay accumulates into the arena: segments that the lazy zero_grad left to their first writer are zeroed first
+        # (solver.FlatArena.claim_replay), and the replay counts as this pass's write of every one of them
+        for a, ps in self._arena_params():
+            a.claim_replay(ps)
         k = next((i for i, t in enumerate(inputs) if t.requires_grad), None)
         if k is not None and torch.is_grad_enabled():
-            params = self.__dict__.get("_params")
-            if params is None:
-                params = self.__dict__["_params"] = tuple(p for p in self.module.parameters() if p.requires_grad)
-            inputs = inputs[:k] + (_SignalAfterBackward.apply(inputs[k], params),) + inputs[k + 1:]
+            inputs = inputs[:k] + (_SignalAfterBackward.apply(inputs[k], self._grad_params()),) + inputs[k + 1:]
         if prof.ON and key in self._work:
             prof.add_replay(self._work[key])
         outs = fn(*inputs)

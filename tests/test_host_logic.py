@@ -619,6 +619,104 @@ def test_lazy_zero_grad_mixed_launch_does_not_accumulate_onto_stale_gradients():
     assert ib not in ar._lazy_pending and ib not in ar.direct
 
 
+def _lazy_generation(ar):
+    """What zero_grad(lazy=True) does on the device, emulated on a CPU arena (which zero-fills everything): the parameters written
+    directly in the previous generation keep their segments and are listed as pending; the rest is zeroed."""
+    keep = {i for i in ar.direct if ar.written[i] == ar.gen}
+    ar.gen += 1
+    for i in range(len(ar.params)):
+        if i not in keep:
+            ar.g[ar.offsets[i]:ar.offsets[i] + ar.sizes[i]].zero_()
+    ar.direct, ar._lazy_pending = set(keep), set(keep)
+    return keep
+
+
+def test_replayed_segment_after_eager_step_neither_accumulates_onto_nor_loses_gradients():
+    """A hipGraph-replayed group (utils/graphs.GraphedSegment) runs no Python and its captured launches accumulate (beta = 1).  After an
+    eager step its parameters are `direct`, so the lazy zero_grad leaves last step's gradient in their segments: the replay's claim
+    (FlatArena.claim_replay) zeroes them first, and counts as this pass's write -- finish_grads keeps what the replay wrote, and an eager
+    launch into the same parameters later in the pass (two forwards before one backward, BSGAL ACTIVE_COMPARE 'all') accumulates."""
+    from divergen_amd.solver import FlatArena
+    m = torch.nn.Module()
+    m.a, m.b, m.c = torch.nn.Linear(8, 8), torch.nn.Linear(8, 6, bias=False), torch.nn.Linear(8, 8, bias=False)
+    ar = FlatArena(m)
+    ar._direct_state()
+    grp = [m.a.weight, m.a.bias, m.b.weight]                 # the replayed group; m.c stays eager throughout
+    ig = [p._dgx_arena_slot[1] for p in grp]
+    ic = m.c.weight._dgx_arena_slot[1]
+    seg = lambda i: ar.g[ar.offsets[i]:ar.offsets[i] + ar.sizes[i]]
+    # step 1: eager -- the grouped weight-gradient launch is the first writer of every segment
+    ar.zero_grad()
+    assert ar.claim_first_write(grp) and ar.claim_first_write([m.c.weight])
+    for i in ig + [ic]:
+        seg(i).fill_(3.0)
+    # step 2: lazy zero_grad keeps the segments, then the group replays
+    assert _lazy_generation(ar) == set(ig + [ic])
+    ar.claim_replay(grp)
+    for i in ig:
+        assert float(seg(i).abs().max()) == 0.0, ar.names[i]           # zeroed BEFORE the replay adds into them
+        assert i not in ar.direct and i not in ar._lazy_pending and ar.written[i] == ar.gen
+    assert float(seg(ic).min()) == 3.0 and ic in ar._lazy_pending     # the eager parameter is untouched
+    for i in ig:
+        seg(i).add_(2.0)                                              # the replay's accumulating launch
+    # a second forward of the same pass issues the group eagerly: it must accumulate onto the replay's gradient
+    assert not ar.claim_first_write(grp)
+    for i in ig:
+        seg(i).add_(1.0)
+    ar.finish_grads()                                                 # (optimizer step / reducer flush)
+    for i in ig:
+        assert float(seg(i).min()) == float(seg(i).max()) == 3.0, ar.names[i]
+    assert float(seg(ic).abs().max()) == 0.0                          # c was not written in step 2: zeroed, not stale
+    # step 3: nothing of the group is direct any more -- the lazy zero_grad fills its segments like everything else
+    assert _lazy_generation(ar) == set()
+    ar.claim_replay(grp)                                              # (a steady replay: nothing pending, nothing zeroed)
+    assert not ar._lazy_pending
+
+
+def test_capture_leaves_gradients_and_first_writer_state_as_it_found_them():
+    """A capture's warm-up passes (torch.cuda.make_graphed_callables, on uninitialised output gradients) write and claim the segment's
+    gradients outside any training step.  FlatArena.grad_state / restore_grad_state around it put segments and bookkeeping back exactly
+    -- also when this generation already wrote into them -- and after the capture step's replay the group is no longer `direct`: the
+    next generation's lazy zero_grad zeroes its segments."""
+    from divergen_amd.solver import FlatArena
+    m = torch.nn.Module()
+    m.a, m.b = torch.nn.Linear(8, 8), torch.nn.Linear(8, 16, bias=False)
+    ar = FlatArena(m)
+    ar._direct_state()
+    grp = [m.a.weight, m.a.bias]
+    ia, ib = [p._dgx_arena_slot[1] for p in grp], m.b.weight._dgx_arena_slot[1]
+    seg = lambda i: ar.g[ar.offsets[i]:ar.offsets[i] + ar.sizes[i]]
+    ar.zero_grad()
+    assert ar.claim_first_write(grp) and ar.claim_first_write([m.b.weight])
+    for i in ia + [ib]:
+        seg(i).fill_(4.0)
+    _lazy_generation(ar)                                      # the group and b pending with last step's gradient
+    assert ar.claim_first_write([m.b.weight])                 # part of this pass already ran: b written
+    seg(ib).fill_(7.0)
+    seg(ia[0])[:5] = torch.arange(5.0)                        # (a distinctive pattern to restore)
+    before = (ar.g.clone(), list(ar.written), set(ar.direct), set(ar._lazy_pending))
+    state = ar.grad_state(grp)
+    # the warm-up: three passes of claims, an ensure_zeroed and garbage writes
+    from divergen_amd.layers.linear_ops import ensure_zeroed
+    ensure_zeroed(m.a.bias)
+    for _ in range(3):
+        ar.claim_first_write(grp)
+        for i in ia:
+            seg(i).fill_(float("nan"))
+    ar.restore_grad_state(state)
+    assert torch.equal(ar.g, before[0]) and ar.written == before[1]
+    assert ar.direct == before[2] and ar._lazy_pending == before[3]
+    # the capture step replays the new graph
+    ar.claim_replay(grp)
+    for i in ia:
+        seg(i).add_(1.0)
+        assert i not in ar.direct
+    ar.finish_grads()
+    assert float(seg(ib).min()) == 7.0 and all(float(seg(i).min()) == float(seg(i).max()) == 1.0 for i in ia)
+    assert _lazy_generation(ar) == {ib}                       # the group's segments are zero-filled for the next step
+    assert all(float(seg(i).abs().max()) == 0.0 for i in ia)
+
+
 def test_box_head_first_fc_is_stored_hwc_and_state_dicts_keep_the_reference_order():
     """FastRCNNConvFCHead keeps fc1's columns in (h, w, c) order (the pooled features are channels-last in memory: flattening is a
     view), while state_dict() / load_state_dict() speak the reference's (c, h, w) order (box_head.py:26-98: nn.Flatten of
