@@ -20,7 +20,6 @@ struct GemmP {
     int splits, kt_per_split;  // split-K: workgroup (tile, s) contracts K-tiles [s * kt_per_split, ...) into ws[s] (fp32)
     float* ws;
     int mode;
-    unsigned long long* dbg; // development: per-workgroup phase timestamps (s_memtime), 8 per workgroup, or null
     uint16_t* C;            // bf16 (M, ldc): modes 0, 1, 2 (pre-activation), 4
     int ldc;
     const uint16_t* bias;   // bf16 (N) or null
@@ -40,7 +39,6 @@ struct GemmP {
     int conv_kc, conv_wp;
     int cmap_n, cmap_h, cmap_w;
     int relu;
-    int krot;
     // grouped implicit convolution (dgx_conv3x3_gemm_multi): ngrp > 0 images that share B / bias / N / K / the epilogue -- the FPN
     // levels under one tower layer -- in ONE launch: tile L belongs to group g = the last one with tile0 <= L; the kernel patches
     // A / C / M and the image geometry from the group's record and goes on as for a single image (no split-K in this form)

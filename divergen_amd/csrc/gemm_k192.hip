@@ -203,7 +203,7 @@ int launch_k192(KwParams& K, hipStream_t st, int grid) {
 // gemm_nt.hip's dispatch hands the K = 192 problems it takes here (bool: the shape and the tail are this kernel's)
 bool dgx_gemm_k192_takes(const GemmP& P) {
     return P.K == 192 && P.lda >= 192 && P.N >= 192 && P.N % 192 == 0 && P.M >= 32768 && !P.conv_kc && P.ngrp == 0 && !P.relu && P.mode >= 0 &&
-           P.mode <= 4 && !P.dbg && ((uintptr_t)P.A & 15) == 0 && ((uintptr_t)P.B & 15) == 0 && (P.lda & 7) == 0 && (P.ldb & 7) == 0;
+           P.mode <= 4 && ((uintptr_t)P.A & 15) == 0 && ((uintptr_t)P.B & 15) == 0 && (P.lda & 7) == 0 && (P.ldb & 7) == 0;
 }
 int dgx_gemm_k192_launch(const GemmP& P0, hipStream_t st) {
     extern int dgx_get_reserved_cus(void);

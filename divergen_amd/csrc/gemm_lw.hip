@@ -24,6 +24,7 @@
 //     with the fused tail (bias | bias + exact GELU with both tensors | x GELU'(f1) | x ReLU'(act) | window-reverse + roll + crop +
 //     DropPath + residual add) of gemm_common.h; stores are not waited for, they drain under the next tile's main loop.
 #include "gemm_common.h"
+#include "dev_clock.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -107,7 +108,6 @@ __global__ __launch_bounds__(LW_THREADS) void gemm_lw_kernel(GemmP P0) {
     const int NTK = (P0.K + GBK - 1) / GBK;
     const int ktail = P0.K - (NTK - 1) * GBK;
     const uint32_t lds0 = (uint32_t)(uintptr_t)(DGX_LDS unsigned char*)lds_raw;
-#define LCLK(i) do { if (P0.dbg && threadIdx.x == 0 && L0 == first) P0.dbg[(size_t)blockIdx.x * 8 + (i)] = __builtin_readcyclecounter(); } while (0)
 
     // item L0 -> tile origin, K range and (grouped convolution) the image the tile belongs to
     auto locate_item = [&](int L0, GemmP& P, LwItem& it) {
@@ -252,7 +252,7 @@ __global__ __launch_bounds__(LW_THREADS) void gemm_lw_kernel(GemmP P0) {
         LwItem it;
         locate_item(L0, P, it);
         const int m0 = it.m0, n0 = it.n0, NT = it.NT;
-        LCLK(0);
+        DGX_CLK(0);
         f32x4 acc[WMF][WNF];
 #pragma unroll
         for (int i = 0; i < WMF; ++i)
@@ -299,7 +299,7 @@ __global__ __launch_bounds__(LW_THREADS) void gemm_lw_kernel(GemmP P0) {
             __builtin_amdgcn_s_setprio(0);
         };
         g_bar();                                   // #0
-        LCLK(1);
+        DGX_CLK(1);
         if (grp == 1) g_bar();                     // #1: one phase behind group 0
         for (int t = 0; t < NT; ++t) {
             read_phase(t);
@@ -310,7 +310,7 @@ __global__ __launch_bounds__(LW_THREADS) void gemm_lw_kernel(GemmP P0) {
             g_bar();                               // group 0: #(2t+2), group 1: #(2t+3)
         }
         if (grp == 0) g_bar();                     // #(2 NT + 1)
-        LCLK(2);
+        DGX_CLK(2);
 
         // ---- split-K: the raw fp32 accumulators go to this split's slab; gemm_nt's fold kernel finishes the job
         if (P0.splits > 1) {
@@ -437,7 +437,7 @@ __global__ __launch_bounds__(LW_THREADS) void gemm_lw_kernel(GemmP P0) {
             for (int j = 0; j < WNF; ++j) asm volatile("" : "+v"(pk[i][j]));      // packed HERE, not lazily in front of each slab
         asm volatile("" ::: "memory");             // (and the tail's operand loads below stay below: they need the registers this frees)
         prefetch(0);
-        LCLK(3);
+        DGX_CLK(3);
 #pragma unroll
         for (int p = 0; p < NPASS; ++p) {
             if (p + 1 < NPASS) prefetch(p + 1);
@@ -476,7 +476,7 @@ __global__ __launch_bounds__(LW_THREADS) void gemm_lw_kernel(GemmP P0) {
         // (a garbage token = a store far outside the tensor: found by tests/test_gpu_pins.py with dgx_set_reserved_cus(16), the first
         // configuration that gives a 128 x 192 residual launch a second item per workgroup).  One more barrier per item, this layout only.
         if constexpr ((MC == 3 || MC == 6) && Cfg::TOK0 < Cfg::RING) { lw_lgkm0(); g_bar(); }
-        LCLK(4);
+        DGX_CLK(4);
     }
 }
 
@@ -530,3 +530,5 @@ int gemm_lw_launch(GemmP& P, int bm, int bn, hipStream_t st) {
     if (bm == 128 && bn == 128) return lw_launch_t<128, 128, 4, 4>(P, st);
     return DGX_ERR_UNSUPPORTED;
 }
+
+DGX_CLK_READER(dgx_dev_gemm_lw_clocks)

@@ -20,8 +20,8 @@
 //     bias + window_reverse/roll/crop + DropPath + residual add | multiply by GELU'(f1)) applied on the way out;
 //   * XCD-aware tile order: workgroups of one XCD (blockIdx % 8) take consecutive tiles = the same A row-panel.
 #include "gemm_common.h"
+#include "dev_clock.h"
 #include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
 namespace {
@@ -38,12 +38,11 @@ template <int BM, int BN, int NS_> struct GemmCfg {
 };
 }  // namespace
 
-// DIAG (development builds only, -DDGX_GEMM_DEV): ablation bits -- 1 no steady-state loads, 2 no MFMAs, 4 no fragment reads
 // MC >= 0: the fused tail is a compile-time constant (2: bias + GELU, 3 / 6: bf16 / fp32 residual, 4: x GELU'(f1)), as in gemm_lw --
 // the two-workgroup instantiation that runs the K <= 768 fused-tail GEMMs.  With the mode a run-time field the tail's operand prefetch
 // sat under mode branches, and the compiler's wait-count model, merging the path without a prefetch, waited for every outstanding load
 // (vmcnt(0)) before the staging pass the prefetch was meant to overlap (round 5, tools/isa_wait_scan.py).  MC = -1: run-time mode.
-template <int BM, int BN, int NS, int MINW, int DIAG = 0, int MC = -1>
+template <int BM, int BN, int NS, int MINW, int MC = -1>
 __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
     if constexpr (MC == 6) { P.mode = 3; P.res_dtype = DGX_F32; }
     else if constexpr (MC == 3) { P.mode = 3; P.res_dtype = DGX_BF16; }
@@ -67,10 +66,8 @@ __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
         P.cmap_n = q.cn; P.cmap_h = q.ch; P.cmap_w = q.cw; P.conv_wp = q.wp;
         L -= q.tile0;
     }
-#define GCLK(i) do { if (P.dbg && threadIdx.x == 0) P.dbg[(size_t)blockIdx.x * 8 + (i)] = __builtin_readcyclecounter(); } while (0)
-#define GCLKR(i) do { if (P.dbg && threadIdx.x == 0) P.dbg[(size_t)blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-    GCLK(0);
-    GCLKR(5);                                      // constant 100 MHz counter next to the shader-clock one: the ratio is the clock
+    DGX_CLK(0);
+    DGX_CLK_RT(5);                                    // constant 100 MHz counter next to the shader-clock one: the ratio is the clock
     const int tm = L / P.tiles_n, tn = L - tm * P.tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
     const int tid = threadIdx.x, l = tid & 63;
@@ -110,12 +107,8 @@ __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
     const uint32_t lds0 = (uint32_t)(uintptr_t)(DGX_LDS unsigned char*)lds_raw;
     const uint32_t ldsw = __builtin_amdgcn_readfirstlane(lds0 + 1024u * w);
     // one of the NL loads of a tile: k < NA -> A rows, else B rows
-    // K rotation (development builds: DGX_GEMM_KROT=1; off in the product): workgroups that share an operand panel walk K from different starting
-    // tiles, so a line fetched from HBM for one is in L2 when the others ask.  Measured (tools/gemm_cold_probe2.py): -7..10 %
-    // when every operand is cold in HBM, +5..12 % when they sit in L2 / the memory-side cache, nothing on the training step.
-    const int rot = (P.krot && NT >= 4) ? ((tm + tn) & 3) * (NT >> 2) : 0;
     auto issue_one = [&](int k, int t, int stage) {
-        const int kta = kt0 + (t + rot >= NT ? t + rot - NT : t + rot);
+        const int kta = kt0 + t;
         const uint32_t soff = (uint32_t)kta * (GBK * 2);
         uint32_t soffA = soff;
         if (P.conv_kc) {                           // implicit convolution: tap shift (rows) + channel block of the tap
@@ -140,14 +133,13 @@ __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
         for (int j = 0; j < WNF; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     bf16x8 af[WMF][2], bfr[WNF][2];
     // LOAD phase of group 0: this wave's NL loads of tile `ti` (if >= 0) into stage `istage`, then the 2 (WMF + WNF) fragment
-    // reads of the tile in `stage`.  Measured (tools/gemm_phase_probe.py): an LDS-direct load costs its wave ~60 cycles of
+    // reads of the tile in `stage`.  Measured (profiles/r04_gemm_nt_phases.txt): an LDS-direct load costs its wave ~60 cycles of
     // issue next to MFMAs or plain code and ~80-180 when it sits between ds_reads, so the loads are kept together.
     auto load_phase = [&](int stage, int ti, int istage) {
         if (ti >= 0) {
 #pragma unroll
             for (int k = 0; k < NL; ++k) issue_one(k, ti, istage);
         }
-        if constexpr ((DIAG & 4) != 0) return;
         DGX_LDS const unsigned char* sa = lds_opaque((const unsigned char*)lds_raw + stage * SB + la);
         DGX_LDS const unsigned char* sa1 = lds_opaque((const unsigned char*)lds_raw + stage * SB + (la ^ 64u));
         DGX_LDS const unsigned char* sb = lds_opaque((const unsigned char*)lds_raw + stage * SB + lb);
@@ -164,8 +156,7 @@ __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
         }
     };
     auto mfmas = [&]() {
-        if constexpr ((DIAG & 2) != 0) return;
-        if constexpr ((DIAG & 8) == 0) __builtin_amdgcn_s_setprio(1);
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int kh = 0; kh < 2; ++kh)
 #pragma unroll
@@ -204,7 +195,7 @@ __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
         else g_vmcnt<0>();
     }
     g_bar();                                       // #0: tile 0 visible to everyone
-    GCLK(1);
+    DGX_CLK(1);
     int rs = 0;                                    // stage of the tile being read
     // Group 0 issues in its LOAD phase, group 1 right AFTER its MFMAs (both in I_{2t+3} for tile t + 2 when NS = 2).
     // Measured per K-tile of a 256x192 tile: loads of group 1 in front of its MFMAs 2525 cycles (their issue time delays the
@@ -217,7 +208,7 @@ __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
             int ti = -1;
             if (t >= 1) {
                 is = is + 1 == NS ? 0 : is + 1;
-                if (t + NS - 1 < NT && !(DIAG & 1)) ti = t + NS - 1;
+                if (t + NS - 1 < NT) ti = t + NS - 1;
             }
             load_phase(rs, ti, is);
             rs = rs + 1 == NS ? 0 : rs + 1;
@@ -239,7 +230,7 @@ __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
             if (t + 1 < NT) wait_tile(t + 1);
             g_bar();                               // #(2t+2)
             mfmas();
-            if (t + NS < NT && !(DIAG & 1)) {
+            if (t + NS < NT) {
 #pragma unroll
                 for (int k = 0; k < NL; ++k) issue_one(k, t + NS, is);
             }
@@ -248,7 +239,7 @@ __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
         }
     }
     g_vmcnt<0>();
-    GCLK(2);
+    DGX_CLK(2);
 
     // ---- split-K: the raw fp32 accumulators go to this split's slab; dgx's fold kernel finishes the job
     if (P.splits > 1) {
@@ -366,7 +357,7 @@ __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
         }
     }
     __syncthreads();
-    GCLK(3);
+    DGX_CLK(3);
 #pragma unroll
     for (int it = 0; it < PFN; ++it) {
         int row, ch, gm, gn;
@@ -390,8 +381,8 @@ __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
     }
 #undef DGX_EPI_PREFETCH
 #undef DGX_EPI_PREFETCH_N
-    GCLK(4);
-    GCLKR(6);
+    DGX_CLK(4);
+    DGX_CLK_RT(6);
 }
 
 // split-K fold: y = bf16(sum_s slab[s] + bias), then the same fused tail; one lane per 8-column chunk
@@ -479,7 +470,7 @@ TileChoice choose_tile(int M, int N) {
     return {bm, bn};
 }
 
-template <int BM, int BN, int NS, int MINW = 2, int DIAG = 0, int MC = -1>
+template <int BM, int BN, int NS, int MINW = 2, int MC = -1>
 int launch_gemm(GemmP& P, hipStream_t st) {
     using Cfg = GemmCfg<BM, BN, NS>;
     const int tiles_m = (P.M + BM - 1) / BM;
@@ -492,12 +483,12 @@ int launch_gemm(GemmP& P, hipStream_t st) {
     P.per_xcd = (P.total * P.splits + 7) / 8;
     static bool once = false;
     if (!once) {
-        if (hipFuncSetAttribute((const void*)gemm_nt_kernel<BM, BN, NS, MINW, DIAG, MC>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS) != hipSuccess)
+        if (hipFuncSetAttribute((const void*)gemm_nt_kernel<BM, BN, NS, MINW, MC>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS) != hipSuccess)
             return DGX_ERR_UNSUPPORTED;
         once = true;
     }
     g_last = {MINW == 4 ? 2 : 0, BM, BN, P.splits};
-    hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, NS, MINW, DIAG, MC>), dim3(8 * P.per_xcd), dim3(512), Cfg::LDS, st, P);
+    hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, NS, MINW, MC>), dim3(8 * P.per_xcd), dim3(512), Cfg::LDS, st, P);
     if (P.splits > 1) {
         const int64_t chunks = (int64_t)P.M * (P.N >> 3);
         const int grid = (int)((chunks + 255) / 256 < 4096 ? (chunks + 255) / 256 : 4096);
@@ -548,10 +539,9 @@ static int dgx_gemm_dispatch(GemmP& P, hipStream_t st);
 static bool use_two_wg(const GemmP& P) {          // see dgx_gemm_dispatch
     return g_dev.two_wg != 0 && P.N % 192 == 0 && P.K <= 768 && P.M >= (g_dev.two_wg >= 2 ? g_dev.two_wg : 4096) && !P.conv_kc;
 }
-static void* g_dbg_buffer = nullptr;
 static FILE* g_gemm_log = nullptr;     // one line per launch (dgx_dev_gemm_log), joined with a kernel trace by tools/gemm_insitu.py
 static FILE* gemm_log_file() { return g_gemm_log; }
-extern "C" void dgx_dev_gemm_set_debug(void* device_buffer) { g_dbg_buffer = device_buffer; }
+DGX_CLK_READER(dgx_dev_gemm_nt_clocks)
 extern "C" int dgx_dev_gemm_log(const char* path) {
     if (g_gemm_log) { fclose(g_gemm_log); g_gemm_log = nullptr; }
     if (path && *path && !(g_gemm_log = fopen(path, "w"))) return DGX_ERR_BAD_ARG;
@@ -595,9 +585,6 @@ extern "C" int dgx_gemm_bf16_nt(const void* A, const void* B, int M, int N, int 
     P.ws = (float*)ep->workspace;
     g_ws_bytes_cur = ep->workspace ? ep->workspace_bytes : 0;
     P.relu = (ep->mode <= DGX_EPI_BIAS) ? ep->relu : 0;
-#ifdef DGX_GEMM_DEV
-    if (const char* kr = getenv("DGX_GEMM_KROT")) P.krot = atoi(kr);     // development build only (tools/gemm_cold_probe2.py)
-#endif
     switch (ep->mode) {
         case DGX_EPI_NONE: case DGX_EPI_BIAS:
             if (!ep->c || ep->ldc < N || (ep->ldc & 7)) return DGX_ERR_BAD_ARG;
@@ -628,30 +615,11 @@ extern "C" int dgx_gemm_bf16_nt(const void* A, const void* B, int M, int N, int 
     }
     hipStream_t st = (hipStream_t)stream;
     const TileChoice tc = choose_tile(M, N);
-    P.dbg = (unsigned long long*)g_dbg_buffer;
     // algorithmic traffic: both operands once, every result tensor once (residual mode: residual in, sum out, no C)
     const double mn = (double)M * N, rsz = ep->residual_dtype == DGX_F32 ? 4.0 : 2.0;
     const double obytes = ep->mode == DGX_EPI_BIAS_RESIDUAL ? 2.0 * rsz * mn : (ep->mode >= DGX_EPI_BIAS_GELU ? 4.0 * mn : 2.0 * mn);   // GELU / GELU' / ReLU': two tensors
     DgxProfScope prof(DGX_PROF_GEMM_NT, stream, 2.0 * mn * K, 2.0 * ((double)M * K + (double)N * K) + obytes);
     if (FILE* lf = gemm_log_file()) { fprintf(lf, "%d %d %d %d %d %d\n", M, N, K, ep->mode, (use_two_wg(P) && !use_lw(P)) ? 128 : tc.bm, tc.bn); fflush(lf); }
-#ifdef DGX_GEMM_DEV
-    if (const char* dg = getenv("DGX_GEMM_DIAG")) {
-        switch (atoi(dg)) {
-            case 1: return launch_gemm<256, 192, 2, 2, 1>(P, st);
-            case 2: return launch_gemm<256, 192, 2, 2, 2>(P, st);
-            case 3: return launch_gemm<256, 192, 2, 2, 3>(P, st);
-            case 4: return launch_gemm<256, 192, 2, 2, 4>(P, st);
-            case 5: return launch_gemm<256, 192, 2, 2, 5>(P, st);
-            case 6: return launch_gemm<256, 192, 2, 2, 6>(P, st);
-            case 7: return launch_gemm<256, 192, 2, 2, 7>(P, st);
-            case 200: return launch_gemm<192, 192, 3, 2, 0>(P, st);
-            case 300: return launch_gemm<128, 192, 4, 2, 0>(P, st);
-            case 302: return launch_gemm<128, 192, 3, 2, 0>(P, st);
-            case 400: return launch_gemm<256, 128, 3, 2, 0>(P, st);
-            default: break;
-        }
-    }
-#endif
     return dgx_gemm_dispatch(P, st);
 }
 
@@ -677,9 +645,9 @@ static int dgx_gemm_dispatch(GemmP& P, hipStream_t st) {
         // DGX_GEMM_2WG=0 switches it off (A/B).
         if (use_two_wg(P)) {
             switch (P.mode) {            // the tails this form exists for, each with its mode compiled in
-                case 2: return launch_gemm<128, 192, 2, 4, 0, 2>(P, st);
-                case 3: return P.res_dtype == DGX_BF16 ? launch_gemm<128, 192, 2, 4, 0, 3>(P, st) : launch_gemm<128, 192, 2, 4, 0, 6>(P, st);
-                case 4: return launch_gemm<128, 192, 2, 4, 0, 4>(P, st);
+                case 2: return launch_gemm<128, 192, 2, 4, 2>(P, st);
+                case 3: return P.res_dtype == DGX_BF16 ? launch_gemm<128, 192, 2, 4, 3>(P, st) : launch_gemm<128, 192, 2, 4, 6>(P, st);
+                case 4: return launch_gemm<128, 192, 2, 4, 4>(P, st);
                 default: return launch_gemm<128, 192, 2, 4>(P, st);
             }
         }
@@ -727,11 +695,11 @@ int launch_gemm_grouped(GemmP& P, const int* Ms, int n, hipStream_t st) {
     P.per_xcd = (P.total + 7) / 8;
     static bool once = false;
     if (!once) {
-        if (hipFuncSetAttribute((const void*)gemm_nt_kernel<BM, BN, NS, MINW, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS) != hipSuccess)
+        if (hipFuncSetAttribute((const void*)gemm_nt_kernel<BM, BN, NS, MINW>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS) != hipSuccess)
             return DGX_ERR_UNSUPPORTED;
         once = true;
     }
-    hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, NS, MINW, 0>), dim3(8 * P.per_xcd), dim3(512), Cfg::LDS, st, P);
+    hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, NS, MINW>), dim3(8 * P.per_xcd), dim3(512), Cfg::LDS, st, P);
     DGX_LAUNCH_CHECK();
     return DGX_OK;
 }

@@ -72,12 +72,6 @@ __device__ __forceinline__ void mfma16_vgpr(f32x4& c, bf16x8 a, bf16x8 b) {
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 }  // namespace
 
-#ifdef DIAG_CLOCK
-__device__ unsigned long long w256_clk[8];
-#define WCLK(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) { const unsigned long long t__ = clock64(); w256_clk[i] += t__ - tprev; tprev = t__; } } while (0)
-#else
-#define WCLK(i)
-#endif
 // LDS image of one operand stage: [32 rows (m)][256 columns] bf16, 512-byte rows, NO padding (a wave-wide
 // LDS-direct load writes 1 KiB = two whole rows).  Bank conflicts of the transpose reads (4 consecutive rows,
 // same columns) are removed by an XOR swizzle of the 16-byte chunk index:  physical = logical ^ ((row & 3) << 1).
@@ -113,13 +107,8 @@ __global__ __launch_bounds__(256) void wgrad256_partial_kernel(Params256 P) {
         q.M = im.M;
         s_in = su - im.slab0;
     }
-#ifdef DIAG_SAMEPANEL   // every workgroup streams the same two panels: isolates the CU-side limit from L2 / fabric
-    const int n0 = 0, k0 = 0;
-    const int m_begin = 0, m_end = min(q.M, q.slab);
-#else
     const int n0 = (tile / q.tiles_k) * T256, k0 = (tile % q.tiles_k) * T256;
     const int m_begin = s_in * q.slab, m_end = min(q.M, m_begin + q.slab);
-#endif
     const int nst = (m_end - m_begin + BM256 - 1) / BM256;
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, g = l >> 4, c16 = l & 15;
     const int wn = (w >> 1) * 128, wk = (w & 1) * 128;    // this wave's quadrant

@@ -16,7 +16,7 @@
 //     pass meet on the same 32 banks: SQ_LDS_BANK_CONFLICT was half of all LDS cycles); fragments by ds_read_b64_tr_b16;
 //   * ONE barrier per half K-tile; dY is loaded 4 halves and X 3 halves ahead of its use;
 //   * NO VALU instruction in the MFMA waves' loop: it is unrolled over the rings' common period (12 halves), every LDS address is a
-//     lane pointer formed once plus an immediate.  Measured (tools/probes/mfma_mix_probe.hip, tools/wgrad_lw_clocks.py): with this
+//     lane pointer formed once plus an immediate.  Measured (tools/probes/mfma_mix_probe.hip, profiles/r04_wgrad_lw_clocks.txt): with this
 //     instruction mix (22 transpose reads per 24 MFMAs and wave) one v_add per fragment costs 15 % of the MFMA rate -- 2 360 -> 2 000
 //     cycles per K-tile here; a VALU instruction of a loader wave waits ~20 cycles for an issue slot, which is why the bias gradient
 //     (column sums of dY on a problem's first tile column) is ones^T x fragment on the matrix pipe, 4 MFMAs per loader wave and half;
@@ -58,14 +58,11 @@ struct WlParams {
     int item0[WL_MAXP];              // first item of problem i (searched with constant indices)
     int n, total, per_xcd;
     float beta;
-    int diag;                        // development builds, DGX_WGRAD_LW_DIAG=1 (timing experiments only, results wrong): every workgroup streams the panels of item 0
 };
 
 __device__ __forceinline__ void wl_load_lds16(uint32_t voff, u32x4 rsrc, uint32_t lds_addr, uint32_t soff) {
-#ifndef WL_NO_DMA              // (timing experiment without the loads)
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds" ::"v"(voff), "s"(rsrc), "s"(lds_addr), "s"(soff)
                  : "memory");
-#endif
 }
 __device__ __forceinline__ u32x4 wl_rsrc(const void* base, uint32_t bytes) {
     const uint64_t a = (uint64_t)base;
@@ -85,22 +82,6 @@ template <int N, int I = 0, typename F> __device__ __forceinline__ void wl_stati
 }
 }  // namespace
 
-#ifdef DGX_GEMM_DEV       // phase time stamps of workgroup 0 (development build only): [wave 0 | wave 4 | wave 8][K-tile][4 stamps], plain stores
-constexpr int WL_CLK_KT = 1024;
-__device__ unsigned long long wl_clk[3 * WL_CLK_KT * 4 + 1];
-#define WLCLK(base, i) do { if (blockIdx.x == 0 && l == 0 && kt < WL_CLK_KT) wl_clk[(((base) >> 2) * WL_CLK_KT + kt) * 4 + (i)] = clock64(); } while (0)
-#define WLCLK0() int kt = 0, itn = 0
-#define WLCLKN() ++kt
-__device__ unsigned long long wl_clk2[3 * 8 * 4];      // per wave, item, {after the last barrier, after the read-out, after barrier #0 of the next item, -}
-#define WLCLKI(base, i) do { if (blockIdx.x == 0 && l == 0 && itn < 8) wl_clk2[(((base) >> 2) * 8 + itn) * 4 + (i)] = clock64(); } while (0)
-#define WLCLKIN() ++itn
-#else
-#define WLCLK(base, i)
-#define WLCLK0()
-#define WLCLKN()
-#define WLCLKI(base, i)
-#define WLCLKIN()
-#endif
 __global__ __launch_bounds__(WL_THREADS) void wgrad_lw_kernel(WlParams P) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds_raw[];
     const int nwx = (int)(gridDim.x >> 3);
@@ -155,8 +136,7 @@ __global__ __launch_bounds__(WL_THREADS) void wgrad_lw_kernel(WlParams P) {
         uint32_t stepA = 0, stepB = 0, sa = 0, sb = 0;     // bytes per granule; ring slots (byte offsets) of those granules
         u32x4 rA, rB;
         auto setup = [&](int L) {
-            locate((P.diag & 1) ? 0 : L, q, n0, k0);
-            if (P.diag & 1) { WlProb q1; int a1, b1; locate(L, q1, a1, b1); q.M = q1.M; }
+            locate(L, q, n0, k0);
             NH = 2 * ((q.M + WL_BM - 1) / WL_BM);
 #pragma unroll
             for (int s = 0; s < 4; ++s) {          // instruction s: rows 8 s + 2 lw + rip
@@ -213,7 +193,6 @@ __global__ __launch_bounds__(WL_THREADS) void wgrad_lw_kernel(WlParams P) {
         };
         auto bias_fold = [&](int f) { bacc[f] = mfma16(ones, bfrag[f], bacc[f]); };
         setup(first);
-        WLCLK0();
         for (int L = first; L < bound; L += nwx) {
             const bool do_bias = q.gb != nullptr && k0 == 0;
             // every slot is free here (barrier E of the previous item); issue order A0 X0 A1 X1 A2 X2 A3 X3 A4, then A(h+5) X(h+4) behind B_h
@@ -226,9 +205,7 @@ __global__ __launch_bounds__(WL_THREADS) void wgrad_lw_kernel(WlParams P) {
                 // before B_h: dY(h+1), X(h+1).  Younger than X(h+1): h = 0: A2 X2 A3 X3 A4; h = 1: A3 X3 A4 A5 X4; h = 2: A4 A5 X4 A6 X5; later:
                 // the four granules issued behind B_(h-2) and B_(h-1)
                 if (h < 3) wl_vmcnt<20>(); else wl_vmcnt<16>();
-                if (lw == 0) WLCLK(8, 0);
                 wl_bar();                          // B_h
-                if (lw == 0) WLCLK(8, 1);
                 if (do_bias) {                     // dY(h)'s rows were read a half ago (their LDS latency hides behind the barrier)
 #pragma unroll
                     for (int s = 0; s < 4; ++s) { issue_a1(s); bias_fold(s); }
@@ -239,9 +216,6 @@ __global__ __launch_bounds__(WL_THREADS) void wgrad_lw_kernel(WlParams P) {
                     issue_a();
                     issue_b();
                 }
-                if (lw == 0) WLCLK(8, 2);
-                if (lw == 0) WLCLK(8, 3);
-                WLCLKN();
             }
             wl_bar();                              // E: every read of this item's granules has fed its MFMA
             if (do_bias) {                         // every row of the 16 x 16 result holds the column sums: lanes 0-15 own one entry per fragment
@@ -280,10 +254,6 @@ __global__ __launch_bounds__(WL_THREADS) void wgrad_lw_kernel(WlParams P) {
     }
 #pragma unroll
     for (int j = 0; j < 3; ++j) pb[j] = lds_opaque(reinterpret_cast<const uint16_t*>(lds_raw + WL_B0 + rowb + 32u * (uint32_t)((3 * wc + j) ^ x ^ (gb << 2))));
-    WLCLK0();
-#ifdef DGX_GEMM_DEV
-    if (blockIdx.x == 0 && tid == 0) { wl_clk2[92] = clock64(); wl_clk2[93] = wall_clock64(); }
-#endif
     for (int L = first; L < bound; L += nwx) {
         WlProb q;
         int n0, k0;
@@ -331,14 +301,10 @@ __global__ __launch_bounds__(WL_THREADS) void wgrad_lw_kernel(WlParams P) {
             __builtin_amdgcn_s_setprio(0);
         };
         wl_bar();                                  // P: dY(0), X(0) landed
-        if (wc == 0) WLCLKI(4 * grp, 2);
-        WLCLKIN();
         wl_static_for<3>([&](auto J) { b0[decltype(J)::value] = fragB(wl_ic<0>{}, J); });
         wl_static_for<PRE>([&](auto I) { afr[decltype(I)::value] = fragA(wl_ic<0>{}, I); });
         for (int h = 0; h < NH; h += 12) {         // NH is even; both rings are back at slot 0 after 12 halves
-            if (wc == 0) WLCLK(4 * grp, 0);
             half(wl_ic<0>{}, b0, b1); half(wl_ic<1>{}, b1, b0);
-            if (wc == 0) WLCLK(4 * grp, 1);
             if (h + 2 >= NH) break;
             half(wl_ic<2>{}, b0, b1); half(wl_ic<3>{}, b1, b0);
             if (h + 4 >= NH) break;
@@ -349,11 +315,8 @@ __global__ __launch_bounds__(WL_THREADS) void wgrad_lw_kernel(WlParams P) {
             half(wl_ic<8>{}, b0, b1); half(wl_ic<9>{}, b1, b0);
             if (h + 10 >= NH) break;
             half(wl_ic<10>{}, b0, b1); half(wl_ic<11>{}, b1, b0);
-            if (wc == 0) WLCLK(4 * grp, 2);
-            WLCLKN();
         }
         wl_bar();                                  // E
-        if (wc == 0) WLCLKI(4 * grp, 0);
         // ---- read-out: fp32 read-modify-write of the gradient straight from the accumulators (16 bytes per lane, 64-byte runs per row)
         const float beta = P.beta;
 #pragma unroll
@@ -370,11 +333,7 @@ __global__ __launch_bounds__(WL_THREADS) void wgrad_lw_kernel(WlParams P) {
                 }
             }
         }
-        if (wc == 0) WLCLKI(4 * grp, 1);
     }
-#ifdef DGX_GEMM_DEV
-    if (blockIdx.x == 0 && tid == 0) { wl_clk2[94] = clock64(); wl_clk2[95] = wall_clock64(); }
-#endif
 }
 
 // The grouped launch.  Returns DGX_ERR_UNSUPPORTED when the group is not this kernel's kind (the caller falls back to wgrad256).
@@ -396,10 +355,6 @@ int wgrad_lw_launch(const dgx_wgrad_problem* pr, int n, float beta, hipStream_t 
     }
     for (int i = 0; i < WL_MAXP; ++i) P.item0[i] = i < n ? P.p[i].item0 : 0x7fffffff;
     P.n = n; P.total = items; P.beta = beta;
-#ifdef DGX_GEMM_DEV
-    static const int diag = getenv("DGX_WGRAD_LW_DIAG") ? atoi(getenv("DGX_WGRAD_LW_DIAG")) : 0;     // development build only (tools/wgrad_lw_clocks.py)
-    P.diag = diag;
-#endif
     P.per_xcd = (items + 7) / 8;
     static bool once = false;
     if (!once) {
@@ -430,10 +385,3 @@ bool wgrad_lw_wants(const dgx_wgrad_problem* pr, int n) {
     return (double)items / (256.0 * rounds) >= 0.74;
 }
 
-#ifdef DGX_GEMM_DEV
-extern "C" int dgx_dev_wl_clocks(unsigned long long* out, int reset) {      // out: 3 * 1024 * 4 stamps
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(wl_clk), sizeof(unsigned long long) * 3 * WL_CLK_KT * 4) != hipSuccess) return -1;
-    if (reset && hipMemcpyFromSymbol(out, HIP_SYMBOL(wl_clk2), sizeof(unsigned long long) * 3 * 8 * 4) != hipSuccess) return -1;     // reset = 1: the item stamps instead
-    return 0;
-}
-#endif

@@ -95,22 +95,6 @@ __device__ __forceinline__ int attn_row(const AttnGeom& G, const WmGeom& g, cons
     return real ? img * (G.H * G.W) + w.base + before : -(1 + img * G.P + (wi * (WS * WS) - w.base) + (n - before));
 }
 
-#ifdef DIAG_CLOCK
-__device__ unsigned long long dgx_clk[16];
-#define CLK(i) do { if (blockIdx.x == 0 && (threadIdx.x & 63) == 0 && (threadIdx.x >> 6) == DIAG_WAVE) { const unsigned long long t__ = clock64(); dgx_clk[i] += t__ - tprev; tprev = t__; } } while (0)
-// forward: the time stamps of wave DIAG_WAVE of EVERY workgroup, kept in registers and stored once at the end (slot 0: start, 1 + i: FCLK(i));
-// an atomic per phase onto one counter made the kernel five times slower
-__device__ unsigned long long dgx_fclk[8192 * 8];
-#define FCLK_START unsigned long long fts[8]; fts[0] = clock64()
-#define FCLK(i) do { fts[1 + (i)] = clock64(); } while (0)
-#define FCLK_END(n) do { if ((threadIdx.x & 63) == 0 && (threadIdx.x >> 6) == DIAG_WAVE && blockIdx.x < 8192) { for (int i__ = 0; i__ <= (n); ++i__) dgx_fclk[blockIdx.x * 8 + i__] = fts[i__]; } } while (0)
-#else
-#define CLK(i)
-#define FCLK(i)
-#define FCLK_START
-#define FCLK_END(n)
-#endif
-
 // Softmax runs in the log2 domain: the bias row is pre-multiplied by log2(e) when it is staged in LDS and the
 // score is one FMA, s2 = qk * (scale*log2e) + bias2 (the -100 of the shift mask becomes -100*log2e), so that
 // p = exp2(s2 - max2) is a bare v_exp_f32.  MASKED = false (W-MSA blocks) drops the region compare entirely.
@@ -138,7 +122,6 @@ __global__ __launch_bounds__(WinCfg<WS>::NT * 64) void win_attn_fwd_kernel(
     int b, h;
     block_to_window_head(blockIdx.x, nH, b, h);
     if (b >= B_) return;
-    FCLK_START;
     const int C = nH * 32;
     const int64_t rowst = 3 * (int64_t)C;
     const uint16_t* base = qkv + (int64_t)b * N * rowst + h * 32;
@@ -185,7 +168,6 @@ __global__ __launch_bounds__(WinCfg<WS>::NT * 64) void win_attn_fwd_kernel(
     const bf16x8 v1 = ld_frag_global(r1 + 2 * C + 8 * (u1 & 3), two && (u1 >> 2) < N);
     const int q_row = COMPACT ? row_of(qok ? qi : 0) : 0;
     const bf16x8 qf = ld_frag_global(COMPACT ? (q_row >= 0 ? qkv + (int64_t)q_row * rowst : G.bias) + h * 32 + 8 * g : base + (int64_t)qi * rowst + 8 * g, qok);
-    FCLK(0);            // address arithmetic + issue
     if (tid < TBL) tbl[tid] = tv * DGX_LOG2E;
     if (tid < NP) {
         const int yk = tid / WS;
@@ -200,9 +182,7 @@ __global__ __launch_bounds__(WinCfg<WS>::NT * 64) void win_attn_fwd_kernel(
         *reinterpret_cast<bf16x8*>(&Ks[(u1 >> 2) * RR + 8 * (u1 & 3)]) = k1;
         *reinterpret_cast<bf16x8*>(&Vs[(u1 >> 2) * RR + 8 * (u1 & 3)]) = v1;
     }
-    FCLK(1);            // the loads' latency + parking in LDS
     __syncthreads();
-    FCLK(2);            // barrier
 
     const int yq = qi / WS, xq = qi - yq * WS;
     const int base_q = qok ? (yq + WS - 1) * (2 * WS - 1) + (xq + WS - 1) : (WS - 1) * (2 * WS - 1) + (WS - 1);
@@ -245,7 +225,6 @@ __global__ __launch_bounds__(WinCfg<WS>::NT * 64) void win_attn_fwd_kernel(
     sum += __shfl_xor(sum, 32);
     if (g == 0 && qok) lse[((int64_t)b * nH + h) * N + qi] = mx * DGX_LN2 + __logf(sum);   // natural-log LSE, as before
     const float inv = 1.0f / sum;
-    FCLK(3);            // scores + softmax
 
     f32x4 o[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     DGX_LDS const uint16_t* v_l4 = tr_lane_ptr(Vs, RR, 4 * g, 0, c16);
@@ -269,8 +248,6 @@ __global__ __launch_bounds__(WinCfg<WS>::NT * 64) void win_attn_fwd_kernel(
         for (int dt = 0; dt < 2; ++dt)
             *reinterpret_cast<u32x2*>(orow + 16 * dt) = u32x2{pack_bf2(o[dt][0] * inv, o[dt][1] * inv), pack_bf2(o[dt][2] * inv, o[dt][3] * inv)};
     }
-    FCLK(4);            // P V + stores issued
-    FCLK_END(5);
 }
 
 // ------------------------------------------------------------------------------------ backward
@@ -434,7 +411,7 @@ __global__ __launch_bounds__((WinCfg<WS>::NT + (HELP ? 3 : 0)) * 64) void win_at
         }
         // (no select on the loaded value here: `if (!kok) P.v = z` made the compiler wait for EVERY load of this prefetch -- vmcnt(0)
         // -- right behind their issue, at the top of phase 1: the whole memory latency of the next window's operands, ~half of the
-        // kernel's time, was exposed in front of the math it was meant to fly under (round 5, tools/r05_attn_variants.sh: removing
+        // kernel's time, was exposed in front of the math it was meant to fly under (round 5 ablation builds, profiles/r05_attn_bwd_phases.txt: removing
         // the exponentials, the metadata reads, the transpose reads or the S / dP MFMAs changed the phase's duration by < 3 % each).
         // Rows past the window (window 7 only) are zeroed where the fragment is consumed.)
     };
@@ -537,7 +514,7 @@ __global__ __launch_bounds__((WinCfg<WS>::NT + (HELP ? 3 : 0)) * 64) void win_at
     // are WRITTEN as the N x N matrix over the staging images (free between two windows), and one lane per table entry adds its pairs
     // up in a fixed order.  Rounds 2-4 reduced them with `ds_add_f32` into an LDS table: LDS float atomics whose lanes share
     // addresses run at about one LANE per two cycles -- 27 600 of them cost every workgroup 24-27 us behind its last window, a third of the
-    // stage-2 launch (45 -> 73 us at 72 x 24; tools/r05_attn_sw.sh ablations; the global float atomics behind them cost 2 us).
+    // stage-2 launch (45 -> 73 us at 72 x 24; ablations in profiles/r05_attn_bwd_phases.txt; the global float atomics behind them cost 2 us).
     // The entries then go to this run's slot of the workspace, and the LAST of the runs that hold a part of head hh (a device counter per
     // head tells which one that is) adds the slots up in slot order onto dtable: one atomic per run and head, and a sum that no longer
     // depends on the order of arrival.  The registers start again at zero.
@@ -548,9 +525,8 @@ __global__ __launch_bounds__((WinCfg<WS>::NT + (HELP ? 3 : 0)) * 64) void win_at
     __shared__ int last_s;
     auto flush_head = [&](int hh) {
         constexpr int TSPLIT_Q = 3;      // = TSPLIT of the window loop
-#ifdef ABL_NOFLUSH      // (tools/r05_attn_sw.sh: no table-gradient reduction at all -- which also lets the compiler drop the 36 accumulations
-        return;         //  per window from the VALU-bound phase 1, so the difference to the kernel as built overstates the flush)
-#endif
+        // (A launch without this flush is not the flush's cost: the compiler then also drops the 36 accumulations per window from the
+        // VALU-bound phase 1.  Flush and slot hand-over against no flush at all: profiles/r05_attn_bwd_phases.txt, 45.5 -> 54.7 us at 72 x 24.)
         DGX_LDS float* M = reinterpret_cast<DGX_LDS float*>(lds_opaque(Qs));
         int krow = key * LDM + 4 * g;
         asm volatile("" : "+v"(krow));   // opaque: keeps the 36 store addresses from being formed above the window loop (registers)
@@ -591,10 +567,6 @@ __global__ __launch_bounds__((WinCfg<WS>::NT + (HELP ? 3 : 0)) * 64) void win_at
             }
             __hip_atomic_store(mine + i, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-#ifdef ABL_NOCOUNT      // (breakdown: the flush without the slot hand-over)
-        __syncthreads();
-        return;
-#endif
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();                 // (the matrix has been read: the images may be staged again)
         if (tid == 0) last_s = __hip_atomic_fetch_add(&head_cnt[hh], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == q_runs + nlrun - 1;
@@ -628,15 +600,8 @@ __global__ __launch_bounds__((WinCfg<WS>::NT + (HELP ? 3 : 0)) * 64) void win_at
         const bool more = done + u + 1 < count;      // another unit in the run: its operands are requested under this one's math
         const bool wrap = u + 1 == seg;              // ... and it is the first unit of the next segment
         const int bn = b + 1 == hi ? lo : b + 1, hn = b + 1 == hi ? h + 1 : h;
-#ifdef DIAG_CLOCK
-        unsigned long long tprev = clock64();
-#endif
-        CLK(0);
         __syncthreads();
-        CLK(1);
-#if !defined(PREFETCH_LATE)
         if (more) issue(bn, hn, P);   // next window's loads fly under this window's math
-#endif
         const bf16x8 kf = *reinterpret_cast<const bf16x8*>(&Ks[(kok ? key : 0) * RR + 8 * g]);
         const bf16x8 vf = *reinterpret_cast<const bf16x8*>(&Vs[(kok ? key : 0) * RR + 8 * g]);
         const int rk = MASKED ? reg_s[kok ? key : 0] : 0;
@@ -674,10 +639,6 @@ __global__ __launch_bounds__((WinCfg<WS>::NT + (HELP ? 3 : 0)) * 64) void win_at
                     const bf16x8 da = *reinterpret_cast<DGX_LDS const bf16x8*>(do_row + 16 * qt * RR);
                     f32x4 lv, dl, bv = {0.f, 0.f, 0.f, 0.f};
                     i32x4 ov = {0, 0, 0, 0}, rv = {0, 0, 0, 0};
-#ifdef ABL_META
-                    if constexpr (PK) { lv = f32x4{scale2, scale2, inv_scale, 0.f}; dl = lv; bv = lv; }
-                    else
-#endif
                     if constexpr (PK) {
                         const wa_f32x2 ld = *reinterpret_cast<DGX_LDS const wa_f32x2*>(ld_lane + 32 * qt);
                         lv = f32x4{quad_bcast<0>(ld.x), quad_bcast<1>(ld.x), quad_bcast<2>(ld.x), quad_bcast<3>(ld.x)};
@@ -693,21 +654,13 @@ __global__ __launch_bounds__((WinCfg<WS>::NT + (HELP ? 3 : 0)) * 64) void win_at
                         ov = *reinterpret_cast<DGX_LDS const i32x4*>(qoff_g + 16 * qt);
                         if (MK) rv = *reinterpret_cast<DGX_LDS const i32x4*>(reg_g + 16 * qt);
                     }
-#ifdef ABL_MFMA1
-                    const f32x4 s = lv + f32x4{bf2f(qa[0]), bf2f(qa[1]), bf2f(kf[0]), bf2f(kf[1])}, dp = dl + f32x4{bf2f(da[0]), bf2f(da[1]), bf2f(vf[0]), bf2f(vf[1])};
-#else
                     const f32x4 s = mfma16(qa, kf, lv);    // s[r]  = S[q 16qt+4g+r][key] - lse[q]/scale
                     const f32x4 dp = mfma16(da, vf, dl);   // dp[r] = dP[q][key] - delta[q]
-#endif
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         float sv = __builtin_fmaf(s[r], scale2, PK ? bv[r] : tbl_k[ov[r]]);       // log2 domain (bias row, lse pre-scaled)
                         if (N % 16 != 0) sv += kneg;
-#ifdef ABL_EXP
-                        pv[r] = sv * 0.001f;
-#else
                         pv[r] = __builtin_amdgcn_exp2f(sv);
-#endif
                         if (MK) pv[r] = rv[r] != rk ? 0.0f : pv[r];
                         dsv[r] = pv[r] * dp[r];
                         dbias[qt < NT ? qt : 0][r] += dsv[r];
@@ -718,13 +671,9 @@ __global__ __launch_bounds__((WinCfg<WS>::NT + (HELP ? 3 : 0)) * 64) void win_at
                 dpk[hh][0] = pack_bf2(dsv[0], dsv[1]);
                 dpk[hh][1] = pack_bf2(dsv[2], dsv[3]);
                 // dS^T image row = key, 4 consecutive queries: one 8-byte store
-#ifndef ABL_DSWRITE
                 if (qt < NT)
                     *reinterpret_cast<DGX_LDS u32x2*>(ds_w + 16 * qt) = u32x2{dpk[hh][0], dpk[hh][1]};
-#endif
-#ifndef NO_HH_BARRIER
                 __builtin_amdgcn_sched_barrier(0);   // one query tile at a time: its 40-odd temporaries die before the next starts
-#endif
             }
             u32x4 a = {ppk[0][0], ppk[0][1], ppk[1][0], ppk[1][1]};
             u32x4 d = {dpk[0][0], dpk[0][1], dpk[1][0], dpk[1][1]};
@@ -733,19 +682,12 @@ __global__ __launch_bounds__((WinCfg<WS>::NT + (HELP ? 3 : 0)) * 64) void win_at
             // B operands = dO / Q rows {32t+4g+j, 32t+16+4g+j} (the k-slot order of P^T / dS^T), by transpose reads
             // swapped operands: D = (dO^T) (P) = dV^T, so a lane ends up with 4 CONSECUTIVE head-dim entries of ONE key
             // (8-byte stores; with P^T as the A operand it held one entry of 4 keys: 2-byte stores, 4 x 32-byte pieces each)
-#ifdef ABL_TR
-            dV[0] = mfma16(pf, pf, dV[0]); dV[1] = mfma16(df, pf, dV[1]); dK[0] = mfma16(pf, df, dK[0]); dK[1] = mfma16(df, df, dK[1]);
-#else
             dV[0] = mfma16(tr_frag(do_l4, 32 * t * RR, (32 * t + 16) * RR), pf, dV[0]);
             dV[1] = mfma16(tr_frag(do_l4, 32 * t * RR + 16, (32 * t + 16) * RR + 16), pf, dV[1]);
             dK[0] = mfma16(tr_frag(q_l4, 32 * t * RR, (32 * t + 16) * RR), df, dK[0]);
             dK[1] = mfma16(tr_frag(q_l4, 32 * t * RR + 16, (32 * t + 16) * RR + 16), df, dK[1]);
-#endif
-#ifndef NO_T_BARRIER
             __builtin_amdgcn_sched_barrier(0);   // keep the t-steps apart: shorter live ranges, no spills
-#endif
         }
-        CLK(2);
         uint16_t* dqb = dqkv + (COMPACT ? (int64_t)0 : (int64_t)b * N * rowst) + h * 32;
         uint32_t row4 = row4_c;
         if (COMPACT) {                   // this lane's key / query: its compact row, or its padding row behind the T real ones
@@ -769,18 +711,13 @@ __global__ __launch_bounds__((WinCfg<WS>::NT + (HELP ? 3 : 0)) * 64) void win_at
         } else if (!shared) {
             store_dkdv();
         }
-        CLK(3);
         __syncthreads();  // dS^T image (and the helpers' partial sums) complete
-        CLK(4);
         if (shared) {
             dV[0] += part_l[0]; dV[1] += part_l[64]; dK[0] += part_l[128]; dK[1] += part_l[192];
             store_dkdv();
         }
         u32x2 dqpk[2] = {{0u, 0u}, {0u, 0u}};
         if (!helper) {                   // phase 2 belongs to the nine query strips
-#if defined(PREFETCH_LATE)
-        if (more) issue(bn, hn, P);   // next window's loads fly under phase 2 (phase 1 has no registers to spare)
-#endif
         // ---- phase 2: dQ strip w = dS[16w.., :] K ; A = dS rows (queries 16w + c16) out of the key-major image
         f32x4 dQ[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
@@ -789,11 +726,9 @@ __global__ __launch_bounds__((WinCfg<WS>::NT + (HELP ? 3 : 0)) * 64) void win_at
             dQ[0] = mfma16(tr_frag(k_l8, 32 * t * RR, (32 * t + 4) * RR), sa, dQ[0]);            // swapped: dQ^T, see dV / dK
             dQ[1] = mfma16(tr_frag(k_l8, 32 * t * RR + 16, (32 * t + 4) * RR + 16), sa, dQ[1]);
         }
-        CLK(5);
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
             dqpk[dt] = u32x2{pack_bf2(dQ[dt][0] * scale, dQ[dt][1] * scale), pack_bf2(dQ[dt][2] * scale, dQ[dt][3] * scale)};
-        CLK(6);
         }
         __syncthreads();                 // this window's LDS consumers are done
         if (more && !wrap) stage();

@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of one environment switch inside ONE gpurun call (same box):  bash tools/ab_env.sh DGX_CONV_WGRAD_MULTI [rounds]
+# A/B of one environment switch inside ONE GPU call (same box):  bash tools/ab_env.sh <VARIABLE> [rounds]
 cd $GRAFT_REPO_ROOT
 for r in $(seq ${2:-2}); do
 for v in 0 1; do

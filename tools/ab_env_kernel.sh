@@ -1,6 +1,6 @@
 #!/bin/bash
 # Average duration of the kernels matching a pattern under the two values of an environment switch, same box:
-#   bash tools/ab_env_kernel.sh DGX_ADAMW_NT adamw
+#   bash tools/ab_env_kernel.sh <VARIABLE> <kernel name pattern>
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 for r in 1 2; do

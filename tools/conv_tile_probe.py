@@ -1,5 +1,5 @@
 """Dev probe: the grouped tower convolution (five FPN levels of 2 x 1024^2, Cin = Cout = 256) and single-image convolutions at the
-mask-head / tower row counts, back to back; run twice with DGX_GEMM_192x256=0 / 1 (tools: A/B of the 192 x 256 tile)."""
+mask-head / tower row counts, back to back."""
 import os
 import sys
 

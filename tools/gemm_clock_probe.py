@@ -1,10 +1,13 @@
 """Shader clock and per-shape time of the own GEMM inside a sustained, cache-cold stream of launches (development).
 
 The eight Linear GEMMs of a Swin-L stage-2 block are launched round-robin for `--iters` rounds on rotating operand copies
-(every operand comes from HBM, as in the training step); HIP events give the time per shape, and the kernel's debug stamps
-(shader-clock counter next to the constant 100 MHz counter) give the clock the CUs actually ran at."""
+(every operand comes from HBM, as in the training step); HIP events give the time per shape, and the phase stamps of gemm_nt
+(csrc/dev_clock.h: shader-clock counter next to the constant 100 MHz counter) give the clock the CUs actually ran at.  Needs the
+development library:  DGX_DEV=1 python -m divergen_amd.csrc.build;  DGX_LIB=divergen_amd/csrc/_obj/dev/libdgx_dev.so python tools/gemm_clock_probe.py"""
 import argparse
 import ctypes
+
+import numpy as np
 import os
 import sys
 
@@ -29,24 +32,23 @@ for name, M, N, K in shapes:
     B = [(torch.randn(N, K, device="cuda", generator=g) * 0.05).to(torch.bfloat16) for _ in range(nc)]
     C = [torch.empty(M, N, device="cuda", dtype=torch.bfloat16) for _ in range(nc)]
     ops.append((A, B, C))
-dbg = torch.zeros(8 * 4096, dtype=torch.int64, device="cuda")
-setdbg = L.lib().dgx_dev_gemm_set_debug
-setdbg.argtypes = [ctypes.c_void_p]
+L.lib().dgx_dev_set(b"gemm_lw", 0)     # gemm_nt everywhere: its stamps are the ones read below
+clocks = L.lib().dgx_dev_gemm_nt_clocks     # development library only
+clocks.argtypes = [ctypes.c_void_p]
+stamps = np.zeros(8 * 4096, dtype=np.uint64)
 ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in shapes] for _ in range(a.iters)]
 for it in range(a.iters):
     for si, (A, B, C) in enumerate(ops):
         k = it % nc
         last = it == a.iters - 1
         if last:
-            dbg.zero_()
-            setdbg(dbg.data_ptr())
+            assert clocks(stamps.ctypes.data) == 0      # clears the stamps of the launches before this one
         ev[it][si][0].record()
         G.gemm_nt(A[k], B[k], out=C[k])
         ev[it][si][1].record()
         if last:
-            torch.cuda.synchronize()
-            setdbg(None)
-            d = dbg.view(-1, 8).cpu()
+            assert clocks(stamps.ctypes.data) == 0
+            d = torch.from_numpy(stamps.astype(np.int64)).view(-1, 8)
             d = d[d[:, 0] > 0]
             cyc = (d[:, 4] - d[:, 0]).double()
             rt = (d[:, 6] - d[:, 5]).double()
