@@ -456,7 +456,9 @@ class DatasetMapper:
 class CopyPasteMapper:
     """CopyPasteMapper.__call__ (mapper.py:856-958) for the shipped configuration: USE_COPY_METHOD 'syn_copy' with an instance
     pool -> InstPool.get_mix_result (divergen_amd/data/copypaste.py, pixels on the GPU compositor); the self-copy branch has
-    no mix results in that configuration, so SimpleCopyPaste returns its input (custom_copypaste.py:254-259)."""
+    no mix results in that configuration, so SimpleCopyPaste returns its input (custom_copypaste.py:254-259).
+    USE_COPY_METHOD 'self_copy' / 'both' / 'p:<f>' (mapper.py:884-936): Simple Copy-Paste from a second training image
+    (custom_copypaste.py:242-341), worker half in _call_self_copy, pixels in dgx_self_copy_paste (_finish_self_copy)."""
 
     def __init__(self, mapper, cfg):
         self.mapper = mapper
@@ -467,9 +469,11 @@ class CopyPasteMapper:
         self.dataset = None
         self.pack = True               # one blob per sample across the process boundary (pack_sample); the loader's finish() unpacks
         self.ring = None               # SlotRing the workers wrote the blobs into (build_detection_train_loader)
-        if self.method not in ("none", "syn_copy"):
-            raise NotImplementedError("INPUT.USE_COPY_METHOD '{}': only 'syn_copy' / 'none' (the shipped configs) are built".format(self.method))
-        if cfg.INPUT.INST_POOL and self.method == "syn_copy":
+        self.self_prob = self._parse_method(self.method)      # None: no self copy; 1.0: always; f: 'p:<f>', per sample
+        self.self_only = self.method == "self_copy"
+        if self.self_prob is not None:
+            self._check_self_copy(cfg)
+        if cfg.INPUT.INST_POOL and self.method != "none" and not self.self_only:
             from .copypaste import InstPool
             if cfg.INPUT.INST_POOL_SAMPLE_TYPE != "cas_random" or cfg.INPUT.INST_POOL_FORMAT != "RGBA":
                 raise NotImplementedError("only INST_POOL_FORMAT 'RGBA' with INST_POOL_SAMPLE_TYPE 'cas_random' is built")
@@ -481,6 +485,45 @@ class CopyPasteMapper:
         self.active_test = cfg.MODEL.get("ACTIVE_TEST", "select")
         self.active_test_one = cfg.MODEL.get("ACTIVE_TEST_INS", "one") == "one" and "one_class" in cfg.INPUT.INST_POOL_SAMPLE_TYPE
         self.per_cat_pool_real = None
+
+    @staticmethod
+    def _parse_method(method):
+        """INPUT.USE_COPY_METHOD (mapper.py:884-890) -> probability of the self-copy branch per sample (None: never taken)."""
+        if method in ("none", "syn_copy"):
+            return None
+        if method in ("self_copy", "both"):
+            return 1.0
+        if isinstance(method, str) and method.startswith("p:"):
+            try:
+                f = float(method[2:])
+            except ValueError:
+                f = float("nan")
+            if not 0.0 <= f <= 1.0:
+                raise ValueError("INPUT.USE_COPY_METHOD '{}': 'p:<f>' needs a probability in [0, 1]".format(method))
+            return f
+        raise NotImplementedError("INPUT.USE_COPY_METHOD '{}': 'none', 'syn_copy', 'self_copy', 'both' and 'p:<f>' are built".format(method))
+
+    @staticmethod
+    def _check_self_copy(cfg):
+        """The self-copy branch is built for SCP_TYPE '', one source image, selected objects, 'basic' blend (the reference's own
+        choice, mapper.py:770); every other switch of that branch is refused by name."""
+        inp = cfg.INPUT
+        refused = [("SCP_TYPE", inp.SCP_TYPE != "", "only '' (a random training image as the source)"),
+                   ("SCP_NUM_SRC", inp.SCP_NUM_SRC != 1, "only 1 (several sources are merged on a temporary canvas first)"),
+                   ("SCP_SRC_OBJ_SELECT", not inp.SCP_SRC_OBJ_SELECT, "only True"),
+                   ("BLANK_RATIO", inp.BLANK_RATIO > 0, "the source is not resized (needs cv2.resize)"),
+                   ("ROTATE_SRC", bool(inp.ROTATE_SRC), "the source is not rotated"),
+                   ("LIMIT_SRC_LSJ", bool(inp.LIMIT_SRC_LSJ), "the source takes the mapper's default augmentations"),
+                   ("RM_BG_PROB", inp.RM_BG_PROB > 0, "background removal is not built"),
+                   ("SCP_RFS", bool(inp.SCP_RFS), "the source index is drawn uniformly"),
+                   ("USE_INSTABOOST", bool(inp.USE_INSTABOOST), "InstaBoost is not built"),
+                   ("USE_COLOR_JITTER", bool(inp.USE_COLOR_JITTER), "colour jitter is not built")]
+        for key, bad, why in refused:
+            if bad:
+                raise NotImplementedError("INPUT.{} {!r} with INPUT.USE_COPY_METHOD '{}': {}".format(key, inp[key], inp.USE_COPY_METHOD, why))
+        if bool(inp.get("ACTIVE_SELECT", False)):
+            raise NotImplementedError("INPUT.ACTIVE_SELECT with INPUT.USE_COPY_METHOD '{}': BSGAL's origin / held-out samples are built "
+                                      "for 'syn_copy' only".format(inp.USE_COPY_METHOD))
 
     def set_dataset(self, dataset):
         self.dataset = dataset
@@ -520,9 +563,12 @@ class CopyPasteMapper:
         result = self.mapper(dataset_dict)
         if "instances" not in result or not result["instances"].has("gt_masks"):        # mapper.py:862-864
             return result
+        idx = None
         if self.use_scp and self.dataset is not None:
             for _ in range(self.num_src):
-                np.random.randint(0, len(self.dataset))
+                idx = np.random.randint(0, len(self.dataset))
+        if self.self_prob is not None and idx is not None:
+            return self._call_self_copy(result, idx)
         if self.inst_pool is None:
             return result
         result = self.inst_pool.prepare(result)
@@ -531,6 +577,63 @@ class CopyPasteMapper:
             result["test_image"], result["test_instances"] = test["image"], test["instances"]
             result["test_image_class"], result["test_file_name"] = cls, test.get("file_name")
         return pack_sample(result) if self.pack else result
+
+    def _call_self_copy(self, result, idx):
+        """The self-copy methods (mapper.py:884-936 + CopyPaste._select_object, custom_copypaste.py:393-411), worker half, in the
+        reference's np.random order: [rand() for 'p:<f>'] -> the source image through the same mapper (its own resize-crop and flip
+        draws) -> the instance pool's draws when the sample takes the pool branch -> m = randint(0, min(ns + 1, 100)),
+        sel = choice(ns, m, replace=False).  Adds `scp_src`: the source image, the m selected masks / boxes / labels in paste order
+        and the canvas size -- what dgx_self_copy_paste needs; the training process runs it (finish)."""
+        from ..layers.copy_paste import self_copy_canvas
+        take_self, take_syn = True, self.method == "both"
+        if self.method.startswith("p:"):
+            take_self = np.random.rand() < self.self_prob
+            take_syn = not take_self
+        src = self.mapper(self.dataset[idx]) if take_self else None
+        if take_syn and self.inst_pool is not None:
+            result = self.inst_pool.prepare(result)
+        if take_self:
+            result = dict(result)
+            si = src["instances"]
+            ns = len(si)
+            m = np.random.randint(0, min(ns + 1, 100))
+            sel = np.random.choice(ns, size=m, replace=False)
+            h1, w1 = result["image"].shape[-2:]
+            if m:
+                sel_t = torch.from_numpy(np.asarray(sel, dtype=np.int64))
+                boxes = si.gt_boxes.tensor[sel_t]
+                H, W = self_copy_canvas((h1, w1), boxes)
+                # only what the canvas can show travels: the source cropped to (H, W) (the kernel zero-pads a smaller one)
+                result["scp_src"] = {"image": src["image"][:, :H, :W].contiguous(),
+                                     "masks": si.gt_masks.tensor.view(torch.uint8)[sel_t][:, :H, :W].contiguous(),
+                                     "boxes": boxes.contiguous(), "labels": si.gt_classes[sel_t].contiguous(), "hw": (H, W)}
+                if self.inst_pool is not None:
+                    self.inst_pool.draw_modes(1)          # blend_image's `random.sample(['basic'], 1)` of this paste (custom_copypaste.py:467)
+            else:                                          # nothing pasted; the Instances is still rebuilt (custom_copypaste.py:311-318)
+                result["scp_src"] = {"image": torch.zeros(3, 0, 0, dtype=torch.uint8), "masks": torch.zeros(0, 0, 0, dtype=torch.uint8),
+                                     "boxes": torch.zeros(0, 4), "labels": torch.zeros(0, dtype=torch.int64), "hw": (int(h1), int(w1))}
+            result["scp_file_name"] = src.get("file_name")
+        return pack_sample(result) if self.pack else result
+
+    @staticmethod
+    def _finish_self_copy(out, scp, dev):
+        """Training-process half of the self copy: ONE dgx_self_copy_paste call on the current stream, then the Instances rebuilt with
+        gt_boxes / gt_classes / gt_masks only (custom_copypaste.py:311-318: instance_source and every other field are gone, also
+        when nothing was pasted)."""
+        from ..layers.copy_paste import self_copy_paste
+        if dev.type != "cuda":
+            raise RuntimeError("INPUT.USE_COPY_METHOD with a self copy needs the GPU compositor (dgx_self_copy_paste); device is %s" % dev)
+        inst = out["instances"]
+        up = lambda t: t.to(dev, non_blocking=True)     # noqa: E731
+        m = int(scp["labels"].shape[0])
+        r = self_copy_paste(out["image"], inst.gt_masks.tensor.view(torch.uint8), inst.gt_boxes.tensor, inst.gt_classes,
+                            up(scp["image"]), up(scp["masks"]), up(scp["boxes"]), up(scp["labels"]), np.arange(m),
+                            canvas_hw=scp["hw"], lazy_masks=True)
+        H, W = (int(v) for v in r["image"].shape[-2:])
+        out["image"], out["height"], out["width"] = r["image"], H, W
+        out["instances"] = Instances((H, W), gt_boxes=Boxes(r["boxes"]), gt_classes=r["labels"],
+                                     gt_masks=BitMasks(r["masks"].view(torch.bool), index=r["keep"]))
+        return out
 
     def finish(self, result, device):
         """What the TRAINING PROCESS runs on one worker result, on the current stream: upload (asynchronous from pinned memory) and
@@ -550,6 +653,9 @@ class CopyPasteMapper:
             out = {k: v for k, v in result.items() if k != "paste_pack"}
             out["image"], out["instances"] = out["image"].to(dev, non_blocking=True), out["instances"].to(dev)
             img, origin = out["image"], out["instances"]
+        scp = out.pop("scp_src", None)
+        if scp is not None:
+            out = self._finish_self_copy(out, scp, dev)
         if self.active_select and "test_image" in out:
             out["origin_image"], out["origin_instances"] = img, origin
             if not origin.has("instance_source"):
@@ -568,13 +674,23 @@ _BLOB_FIELDS = (("image", lambda d: d["image"]), ("gt_masks", lambda d: d["insta
                 ("flat", lambda d: d["paste_pack"]["flat"]), ("desc", lambda d: d["paste_pack"]["desc"]), ("labels", lambda d: d["paste_pack"]["labels"]))
 
 
+# optional sections, present only in a sample that carries a self-copy source (CopyPasteMapper._call_self_copy)
+_BLOB_SCP_FIELDS = (("scp_image", lambda d: d["scp_src"]["image"]), ("scp_masks", lambda d: d["scp_src"]["masks"]),
+                    ("scp_boxes", lambda d: d["scp_src"]["boxes"]), ("scp_labels", lambda d: d["scp_src"]["labels"]))
+
+
 def pack_sample(d):
     """Worker side: the sample's tensors -> d['blob'] (uint8) + d['blob_layout'] [(name, dtype, shape, byte offset)]; the tensor
-    entries themselves are dropped.  Samples without paste_pack / instances pass through unchanged."""
-    if "paste_pack" not in d or "instances" not in d or not d["instances"].has("gt_masks"):
+    entries themselves are dropped.  Samples without paste_pack / instances pass through unchanged.  Sections: the four of the
+    sample, the three of paste_pack when it has one, the four of the self-copy source (scp_src) when it has one; a sample
+    without scp_src packs exactly as it always did."""
+    if ("paste_pack" not in d and "scp_src" not in d) or "instances" not in d or not d["instances"].has("gt_masks"):
         return d
+    fields = _BLOB_FIELDS if "paste_pack" in d else _BLOB_FIELDS[:4]
+    if "scp_src" in d:
+        fields = fields + _BLOB_SCP_FIELDS
     parts, layout, off = [], [], 0
-    for name, get in _BLOB_FIELDS:
+    for name, get in fields:
         t = get(d).contiguous()
         raw = t.view(-1).view(torch.uint8) if t.numel() else torch.zeros(0, dtype=torch.uint8)
         layout.append((name, str(t.dtype).replace("torch.", ""), tuple(t.shape), off))
@@ -583,10 +699,14 @@ def pack_sample(d):
         if pad:
             parts.append(torch.zeros(pad, dtype=torch.uint8))
         off += raw.numel() + pad
-    out = {k: v for k, v in d.items() if k not in ("image", "instances", "paste_pack")}
+    out = {k: v for k, v in d.items() if k not in ("image", "instances", "paste_pack", "scp_src")}
     out["blob"], out["blob_layout"] = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.uint8), layout
-    out["blob_hw"], out["blob_K"] = tuple(d["image"].shape[-2:]), int(d["paste_pack"]["K"])
-    modes = d["paste_pack"].get("modes")
+    out["blob_hw"] = tuple(d["image"].shape[-2:])
+    if "scp_src" in d:
+        out["blob_scp_hw"] = tuple(int(v) for v in d["scp_src"]["hw"])
+    if "paste_pack" in d:
+        out["blob_K"] = int(d["paste_pack"]["K"])
+    modes = d["paste_pack"].get("modes") if "paste_pack" in d else None
     if modes is not None and np.asarray(modes).any():
         # K blend-mode bytes, read by the host when it launches the compositor (so not in the blob), as a numpy array: it pickles
         # inline, where a tensor would cost the training thread a shared-memory handle round trip.  All 'basic' (the shipped
@@ -621,9 +741,13 @@ def unpack_sample(d, device, ring=None):
     for k, v in d.get("blob_extra_fields", {}).items():
         inst.set(k, v.to(device) if hasattr(v, "to") else v)
     out["instances"] = inst
-    out["paste_pack"] = {"flat": f["flat"], "desc": f["desc"], "labels": f["labels"], "K": d["blob_K"]}
-    if d.get("blob_modes") is not None:
-        out["paste_pack"]["modes"] = d["blob_modes"]
+    if "flat" in f:
+        out["paste_pack"] = {"flat": f["flat"], "desc": f["desc"], "labels": f["labels"], "K": d["blob_K"]}
+        if d.get("blob_modes") is not None:
+            out["paste_pack"]["modes"] = d["blob_modes"]
+    if "scp_image" in f:
+        out["scp_src"] = {"image": f["scp_image"], "masks": f["scp_masks"], "boxes": f["scp_boxes"], "labels": f["scp_labels"],
+                          "hw": tuple(d["blob_scp_hw"])}
     return out
 
 
@@ -820,9 +944,12 @@ def build_detection_train_loader(cfg, per_gpu, device, seed):
     pin_thread, ring = on_gpu and DEV["pin"] == "loader", None
     if on_gpu and nw > 0 and DEV["pin"] == "ring":
         # one slot holds an image with up to ~45 ground-truth masks at TRAIN_SIZE^2 (more: that sample takes the ordinary way)
+        # with a self-copy method the sample also carries the source image (3 planes) and up to 99 selected source masks, each at most
+        # TRAIN_SIZE^2: room for ~45 more planes (the mean of the draw over a 90-object image); beyond that, the ordinary way again
         size = int(cfg.INPUT.TRAIN_SIZE)
+        planes = 48 if mapper.self_prob is None else 96
         try:
-            ring = SlotRing(nw, (int(cfg.DATALOADER.PREFETCH_FACTOR) + 2) * per_gpu, size * size * 48 + (8 << 20))
+            ring = SlotRing(nw, (int(cfg.DATALOADER.PREFETCH_FACTOR) + 2) * per_gpu, size * size * planes + (8 << 20))
         except Exception as e:
             logger.warning("loader: no page-locked slot ring (%s); falling back to the DataLoader's pin thread", e)
             pin_thread = True

@@ -139,3 +139,67 @@ def copy_paste(image, masks, boxes, labels, pastes, lazy_masks=False, modes=None
     else:
         out["masks"] = out_masks.index_select(0, keep)
     return out
+
+
+SELF_COPY_MAX = 99      # dgx_self_copy_paste: m <= 99 (the reference draws m < min(ns + 1, 100))
+
+
+def self_copy_canvas(dst_hw, sel_boxes):
+    """(H, W) of the canvas of one self copy (custom_copypaste.py:343-353): the destination size, grown to the ceil of the largest
+    y2 / x2 among the SELECTED source boxes (host data: numpy / CPU tensor (m, 4), m > 0)."""
+    import math
+    b = sel_boxes.cpu().numpy() if isinstance(sel_boxes, torch.Tensor) else np.asarray(sel_boxes)
+    return max(int(dst_hw[0]), math.ceil(b[..., 3].max())), max(int(dst_hw[1]), math.ceil(b[..., 2].max()))
+
+
+def self_copy_paste(image, masks, boxes, labels, src_image, src_masks, src_boxes, src_labels, sel, canvas_hw=None, lazy_masks=False):
+    """Simple Copy-Paste between two real images, one paste step (CopyPaste._scp_src_to_dst + _copy_paste,
+    DG/divergen/data/transforms/custom_copypaste.py:343-389, :428-506, 'basic' blend) in ONE dgx_self_copy_paste call.
+    image uint8 (3,h1,w1), masks uint8 (n0,h1,w1), boxes f32 (n0,4), labels i64 (n0): the destination, GPU tensors.
+    src_image uint8 (3,hs,ws), src_masks uint8 (ns,hs,ws), src_boxes f32 (ns,4), src_labels i64 (ns): the source, GPU tensors.
+    sel: the m <= 99 source objects to paste, in paste order (host integers, each in [0, ns)).
+    canvas_hw: (H, W) when the caller already holds it (the loader's workers do); None reads the selected boxes back.
+    Returns dict(image, masks, boxes, labels) like copy_paste (no `source`): the surviving destination objects with the boxes of their
+    updated masks, then the m selected source objects with their own boxes -- ONE compaction by out_valid.  m == 0: nothing is
+    pasted, the inputs come back as they are (the reference keeps the destination's boxes then).
+    lazy_masks: `masks` holds ALL n0 + m rows and `keep` (i64) the rows of the surviving objects, for BitMasks(masks, index=keep)."""
+    dev = image.device
+    sel = np.asarray(sel, dtype=np.int64).reshape(-1)
+    m, n0, ns = int(sel.shape[0]), int(masks.shape[0]), int(src_masks.shape[0])
+    h1, w1 = int(image.shape[1]), int(image.shape[2])
+    if m > SELF_COPY_MAX:
+        raise ValueError("self_copy_paste: %d source objects selected, at most %d" % (m, SELF_COPY_MAX))
+    if m and (int(sel.min()) < 0 or int(sel.max()) >= ns):
+        raise ValueError("self_copy_paste: selected source index outside [0, %d): %s" % (ns, sel.tolist()))
+    if m == 0:
+        out = dict(image=image, masks=masks, boxes=boxes, labels=labels)
+        if lazy_masks:
+            out["keep"] = torch.arange(n0, dtype=torch.int64, device=dev)
+        return out
+    sel_t = upload_i32(sel, dev)
+    sel_boxes = src_boxes.float().index_select(0, sel_t.long())
+    H, W = (int(v) for v in canvas_hw) if canvas_hw is not None else self_copy_canvas((h1, w1), sel_boxes)
+    image, masks, boxes0 = image.contiguous(), masks.contiguous(), boxes.float().contiguous()
+    src_image, src_masks = src_image.contiguous(), src_masks.contiguous()
+    hs, ws = int(src_image.shape[1]), int(src_image.shape[2])
+    if tuple(masks.shape[1:]) != (h1, w1) or tuple(src_masks.shape[1:]) != (hs, ws):
+        raise ValueError("self_copy_paste: masks %s / %s do not match their images %s / %s" % (
+            tuple(masks.shape), tuple(src_masks.shape), (h1, w1), (hs, ws)))
+    out_image = torch.empty(3, H, W, dtype=torch.uint8, device=dev)
+    out_masks = torch.empty(n0 + m, H, W, dtype=torch.uint8, device=dev)
+    out_boxes = torch.empty(n0, 4, dtype=torch.float32, device=dev)
+    out_valid = torch.empty(n0, dtype=torch.uint8, device=dev)
+    work = torch.empty(((n0 * 5 + 3) & ~3) + H * ((W + 15) // 16) * 4, dtype=torch.int32, device=dev)
+    L.check(L.lib().dgx_self_copy_paste(L.ptr(image), L.ptr(masks) if n0 else None, L.ptr(boxes0) if n0 else None, n0, h1, w1,
+                                        L.ptr(src_image), L.ptr(src_masks), ns, hs, ws, L.ptr(sel_t), m, H, W,
+                                        L.ptr(out_image), L.ptr(out_masks), L.ptr(out_boxes) if n0 else None,
+                                        L.ptr(out_valid) if n0 else None, L.ptr(work), L.stream()), "dgx_self_copy_paste")
+    keep = torch.cat([out_valid, torch.ones(m, dtype=torch.uint8, device=dev)]).nonzero().squeeze(1)      # ONE compaction
+    all_boxes = torch.cat([out_boxes, sel_boxes])
+    all_labels = torch.cat([labels.to(torch.int64), src_labels.to(torch.int64).index_select(0, sel_t.long())])
+    out = dict(image=out_image, boxes=all_boxes.index_select(0, keep), labels=all_labels.index_select(0, keep))
+    if lazy_masks:
+        out["masks"], out["keep"] = out_masks, keep
+    else:
+        out["masks"] = out_masks.index_select(0, keep)
+    return out

@@ -330,6 +330,33 @@ int dgx_copy_paste_blend(uint8_t* image, const uint8_t* masks, const float* boxe
                          const uint8_t* src_rgba, const int32_t* src_desc, int K, uint8_t* out_masks,
                          float* out_boxes, uint8_t* out_valid, int32_t* stats, const uint8_t* modes_host, void* stream);
 
+/* Self copy-paste: Simple Copy-Paste between two real images (INPUT.USE_COPY_METHOD 'self_copy' / 'both' / 'p:<f>'), ONE paste step
+ * of m selected full-frame instance masks of a source image onto a destination, 'basic' blend.  Replaces the numpy passes of
+ * CopyPaste._scp_src_to_dst / _copy_paste / get_updated_masks / get_bboxes: DG/divergen/data/transforms/custom_copypaste.py:343-389,
+ * :413-506 (pad_to_hw, composed mask, mask update, boxes from the updated masks, occlusion filter, image select).
+ *   dst_image u8 (3,h1,w1), dst_masks u8 (n0,h1,w1) 0/1 bytes, dst_boxes0 f32 (n0,4) the destination boxes BEFORE the paste
+ *   src_image u8 (3,hs,ws), src_masks u8 (ns,hs,ws) 0/1 bytes; sel i32 (m) in DEVICE memory: the source planes to paste, in
+ *   paste order, each in [0, ns) (the caller checks; an index outside reads as an empty mask)
+ *   canvas (H, W), H >= h1, W >= w1, chosen by the caller (max of the destination size and the ceil of the selected source
+ *   boxes' largest y2 / x2).  The destination is zero-padded to (H, W); the source is zero-padded OR CROPPED to (H, W).  Rows and
+ *   columns beyond (h1, w1) / (hs, ws) read as 0 and are never fetched.
+ * With composed = any(selected source masks) per canvas pixel:
+ *   out_image u8 (3,H,W)      source pixel where composed, else destination pixel
+ *   out_masks u8 (n0+m,H,W)   rows < n0: destination mask with composed pixels cleared (bytes pass through);
+ *                             row n0+j: source plane sel[j] cropped / padded, untouched otherwise
+ *   out_boxes f32 (n0,4)      box of the updated destination mask (x_min, y_min, x_max + 1, y_max + 1; zeros when empty)
+ *   out_valid u8 (n0)         1 when all |out_box - dst_box0| <= 10 or more than 300 mask pixels survive; m == 0: always 1
+ * The source objects keep the boxes the caller holds; the host compacts the destination rows by out_valid (order preserved).
+ * Every byte of the four outputs is written.  workspace: i32, 16-byte aligned, ((n0 * 5 + 3) & ~3) + H * ((W + 15) / 16) * 4 words
+ * (per-object count / extents, then the composed byte plane with rows padded to 16 pixels).
+ * Limits and errors: m <= 99, H >= h1, W >= w1, h1, w1 > 0, m > 0 needs ns, hs, ws > 0; n0 == 0, m == 0 and ns == 0 are legal.
+ * Anything else, a NULL pointer that would be read or written, or a misaligned workspace -> DGX_ERR_BAD_ARG, nothing launched.
+ * H * W >= 2^31 -> DGX_ERR_UNSUPPORTED.  Sizes need not be multiples of 16 (tail lanes fall back to byte accesses). */
+int dgx_self_copy_paste(const uint8_t* dst_image, const uint8_t* dst_masks, const float* dst_boxes0, int n0, int h1, int w1,
+                        const uint8_t* src_image, const uint8_t* src_masks, int ns, int hs, int ws,
+                        const int32_t* sel, int m, int H, int W, uint8_t* out_image, uint8_t* out_masks,
+                        float* out_boxes, uint8_t* out_valid, int32_t* workspace, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Fused parameter update over a flat arena: per-element gradient value clip, AdamW, EMA lerp of
  * the PRE-step weights (the reference updates the EMA before optimizer.step: DG/train_net.py:262-284),

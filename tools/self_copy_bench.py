@@ -1,0 +1,74 @@
+"""Time the self copy-paste kernels (dgx_self_copy_paste) on the 1024 x 1024 case of tests/test_gpu_self_copy.py (n0 = 20 destination
+objects, ns = 40 source objects, m = 25 selected) next to the pool compositor (dgx_copy_paste, n0 = 10, K = 19: the problem of
+tools/compositor_modes_bench.py) in the same process.  Device-event timing around `--iters` calls after `--warmup`; one JSON line.
+
+    python tools/self_copy_bench.py [--iters 100] [--out FILE]
+    rocprofv3 --kernel-trace --stats -d DIR -o selfcopy -- python tools/self_copy_bench.py --iters 50
+
+The outputs are checked against tests/_selfcopy_ref.py once before timing (a wrong kernel is not timed).  Algorithmic bytes of one
+self copy: (n0 + m) * H * W * 2 + 9 * H * W (every mask plane read and written once, two images read, one written)."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
+
+from divergen_amd import layers as la  # noqa: E402
+from divergen_amd.layers.copy_paste import pack_pastes  # noqa: E402
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--iters", type=int, default=100)
+    p.add_argument("--warmup", type=int, default=10)
+    p.add_argument("--out", default=None)
+    a = p.parse_args()
+    assert torch.cuda.is_available(), "self_copy_bench needs a GPU"
+    import _selfcopy_ref as SR
+    from compositor_modes_bench import problem
+    from test_gpu_self_copy import _scene
+    dev = "cuda:0"
+    size, n0, ns, m = 1024, 20, 40, 25
+    rng = np.random.default_rng(1024)
+    dst, src = _scene(rng, n0, size, size), _scene(rng, ns, size, size)
+    sel = rng.permutation(ns)[:m]
+    d = [torch.from_numpy(x).to(dev) for x in dst]
+    s = [torch.from_numpy(x).to(dev) for x in src]
+    ref = SR.self_copy(*dst, *src, sel)
+    got = la.self_copy_paste(*d, *s, sel, canvas_hw=(size, size))
+    for k in ("image", "masks", "boxes", "labels"):
+        assert np.array_equal(got[k].cpu().numpy(), ref[k]), k
+    img, masks, boxes, labels, pastes = problem()
+    c = [torch.from_numpy(x).to(dev) for x in (img, masks, boxes, labels)]
+    pk = pack_pastes(pastes, dev)
+    calls = {"self_copy": lambda: la.self_copy_paste(*d, *s, sel, canvas_hw=(size, size), lazy_masks=True),
+             "copy_paste_k19": lambda: la.copy_paste(*c, pk, lazy_masks=True)}
+    nbytes = (n0 + m) * size * size * 2 + 9 * size * size
+    res = {"what": "1 image 1024x1024; self copy n0=20 ns=40 m=25; pool compositor n0=10 K=19; ms per call (device events, %d calls)" % a.iters,
+           "self_copy_algorithmic_bytes": nbytes}
+    for name, fn in calls.items():
+        for _ in range(a.warmup):
+            fn()
+        torch.cuda.synchronize()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(a.iters):
+            fn()
+        t1.record()
+        torch.cuda.synchronize()
+        res["ms_" + name] = round(t0.elapsed_time(t1) / a.iters, 4)
+    res["self_copy_GBps_per_call"] = round(nbytes / (res["ms_self_copy"] * 1e-3) / 1e9, 1)
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
