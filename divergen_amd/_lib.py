@@ -119,6 +119,11 @@ SIGNATURES = {
     "dgx_centernet_label_inds": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p]),
     "dgx_copy_paste": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p]),
     "dgx_copy_paste_blend": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "dgx_copy_paste_blend_ws": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_size_t, c_p]),
+    "dgx_poisson_blend": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p, ctypes.c_size_t, c_i, c_p]),
+    "dgx_poisson_work_bytes": (c_i64, [c_i, c_i, c_i64]),
+    "dgx_poisson_frame_unknowns": (c_i64, [c_i, c_i]),
+    "dgx_poisson_max_iter": (c_i, [c_i, c_i, c_i64]),
     "dgx_self_copy_paste": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     "dgx_im2col3x3": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     "dgx_col2im3x3": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),

@@ -157,6 +157,10 @@ def get_cfg():
     #   INPUT.INST_POOL_SHARDS: directory of pool-*.dgxpool shards (divergen_amd/data/pool_store.py, built by
     #   tools/build_inst_pool.py); when set, pool instances are read from the shards instead of PIL-opened per sample.
     cfg.INPUT.INST_POOL_SHARDS = ""
+    #   INPUT.CP_POISSON: admits 'possion' (Poisson blending) to INPUT.CP_METHOD.  Off by default: a 'possion' paste costs one
+    #   conjugate-gradient solve on the device and rewrites the image frame, as the reference's poisson_edit does
+    #   (divergen_amd/csrc/poisson_blend.hip); without the key 'possion' is refused at start-up.
+    cfg.INPUT.CP_POISSON = False
     #   SOLVER.ALLREDUCE_DTYPE: "fp32" (the reference's DDP: gradients all-reduced as they are) or "bf16" (gradient buckets go over
     #   xGMI as bf16, half the bytes per step; engine/ddp.py ArenaReducer(wire_dtype=...)).
     cfg.SOLVER.ALLREDUCE_DTYPE = "fp32"

@@ -12,6 +12,7 @@
 //   k4 masks        : final masks of all objects, 16 pixels per lane, the cover words read once per pixel group
 // With a non-'basic' blend mode among the pastes, k1 is cp_blend_kernel (same cover words, per-tile blend fold) instead.
 #include "dgx_common.h"
+#include "poisson_blend.h"
 
 #define CP_MAX_K 31
 
@@ -258,7 +259,7 @@ __global__ __launch_bounds__(256) void cp_masks_kernel(const uint8_t* __restrict
 // and takes separable 5-tap integer sums.  The library is built with -ffp-contract=off; keep it that way.
 constexpr int CP_TX = 32, CP_TY = 8, CP_HALO = 2;
 constexpr int CP_LX = CP_TX + 2 * CP_HALO, CP_LY = CP_TY + 2 * CP_HALO;
-enum { CP_BASIC = 0, CP_ALPHA = 1, CP_GAUSSIAN = 2 };
+enum { CP_BASIC = 0, CP_ALPHA = 1, CP_GAUSSIAN = 2, CP_POISSON = 3 };
 struct CpModes { uint8_t m[CP_MAX_K + 1]; };        // by-value kernel argument: the host decides, nothing is read back
 struct CpBlurTable { float v[26]; };
 constexpr CpBlurTable cp_blur_table() {
@@ -274,10 +275,14 @@ __device__ __forceinline__ int cp_reflect101(int i, int n) {     // exact for i 
     return min(max(i, 0), n - 1);
 }
 
+// SEG (dgx_copy_paste_blend_ws with a 'possion' paste among the K): the fold covers only the pastes k0 <= k < k1 that are not
+// 'possion' (those are solved between two such launches, poisson_blend.hip), and only the launch with write_cover writes the cover
+// words (of all K pastes).  SEG = false is the kernel of dgx_copy_paste_blend, unchanged.
+template <bool SEG>
 __global__ __launch_bounds__(CP_TX * CP_TY) void cp_blend_kernel(uint8_t* __restrict__ image, int H, int W,
                                                                  const uint8_t* __restrict__ rgba,
                                                                  const int32_t* __restrict__ desc, int K, CpModes modes,
-                                                                 uint32_t* __restrict__ cover) {
+                                                                 uint32_t* __restrict__ cover, int k0, int k1, int write_cover) {
     __shared__ int32_t d[CP_MAX_K * 5];
     __shared__ uint8_t fp[CP_LY][CP_LX];           // footprint bits of the tile + halo (reflect-101 coordinates)
     __shared__ uint8_t hs[CP_LY][CP_TX];           // horizontal 5-tap sums
@@ -294,11 +299,13 @@ __global__ __launch_bounds__(CP_TX * CP_TY) void cp_blend_kernel(uint8_t* __rest
     for (int k = 0; k < K; ++k) {                  // block-uniform: pastes whose (expanded) rectangle misses the tile are skipped
         const int h = d[5 * k + 1], w = d[5 * k + 2], dx = d[5 * k + 3], dy = d[5 * k + 4];
         const int mode = modes.m[k];
-        const int e = mode == CP_GAUSSIAN ? CP_HALO : 0;
+        const bool fold = !SEG || (k >= k0 && k < k1 && mode != CP_POISSON);
+        if (SEG && !fold && !write_cover) continue;
+        const int e = (fold && mode == CP_GAUSSIAN) ? CP_HALO : 0;
         if (dx - e >= tx0 + CP_TX || dx + w + e <= tx0 || dy - e >= ty0 + CP_TY || dy + h + e <= ty0) continue;
         const uint8_t* patch = rgba + d[5 * k];
         int cnt = 0;
-        if (mode == CP_GAUSSIAN) {
+        if (fold && mode == CP_GAUSSIAN) {
             for (int i = threadIdx.x; i < CP_LY * CP_LX; i += blockDim.x) {
                 const int gy = cp_reflect101(ty0 - CP_HALO + i / CP_LX, H), gx = cp_reflect101(tx0 - CP_HALO + i % CP_LX, W);
                 const int sx = gx - dx, sy = gy - dy;
@@ -319,6 +326,7 @@ __global__ __launch_bounds__(CP_TX * CP_TY) void cp_blend_kernel(uint8_t* __rest
         const uint8_t* px = inrect ? patch + 4 * ((int64_t)sy * w + sx) : nullptr;
         const int a = inrect ? px[3] : 0;
         if (a > 0) bits |= 1u << k;
+        if (SEG && !fold) continue;
         if (mode == CP_GAUSSIAN ? cnt == 0 : a == 0) continue;    // the blend leaves D exactly as it is there
         if (!loaded) { r = image[p]; g = image[HW + p]; b = image[2 * HW + p]; loaded = true; }
         const int s0 = inrect ? px[0] : 0, s1 = inrect ? px[1] : 0, s2 = inrect ? px[2] : 0;
@@ -337,7 +345,7 @@ __global__ __launch_bounds__(CP_TX * CP_TY) void cp_blend_kernel(uint8_t* __rest
         }
     }
     if (!inside) return;
-    cover[p] = bits;
+    if (!SEG || write_cover) cover[p] = bits;
     if (loaded) {
         image[p] = (uint8_t)r;
         image[HW + p] = (uint8_t)g;
@@ -346,9 +354,11 @@ __global__ __launch_bounds__(CP_TX * CP_TY) void cp_blend_kernel(uint8_t* __rest
 }
 
 // modes == nullptr: the 'basic' path of every round (cp_cover_blend_kernel); otherwise cp_blend_kernel writes image + cover.
+// pb_work != nullptr (dgx_copy_paste_blend_ws with a 'possion' paste): the image is folded in segments, the pastes between two
+// 'possion' ones by cp_blend_kernel<true>, each 'possion' paste by the solver of poisson_blend.hip, in the order 0..K-1.
 static int cp_launch(uint8_t* image, const uint8_t* masks, const float* boxes0, int n0, int H, int W, const uint8_t* src_rgba,
                      const int32_t* src_desc, int K, uint8_t* out_masks, float* out_boxes, uint8_t* out_valid, int32_t* stats,
-                     const CpModes* modes, void* stream) {
+                     const CpModes* modes, void* stream, void* pb_work = nullptr, int64_t pb_nmax = 0) {
     hipStream_t st = (hipStream_t)stream;
     // cover words live at the tail of the stats workspace: (n0+K)*(K+1)*5 ints, rounded up to a 16-byte boundary, then H*W words
     const int64_t ns = (int64_t)(n0 + K) * (K + 1) * 5;
@@ -356,9 +366,27 @@ static int cp_launch(uint8_t* image, const uint8_t* masks, const float* boxes0, 
     uint32_t* cover = reinterpret_cast<uint32_t*>(stats + ((ns + 3) & ~(int64_t)3));
     const int64_t HW = (int64_t)H * W;
     hipLaunchKernelGGL(cp_stats_init_kernel, dim3((int)((ns + 255) / 256)), dim3(256), 0, st, stats, ns);
-    if (modes) {
-        hipLaunchKernelGGL(cp_blend_kernel, dim3((W + CP_TX - 1) / CP_TX, (H + CP_TY - 1) / CP_TY), dim3(CP_TX * CP_TY), 0, st,
-                           image, H, W, src_rgba, src_desc, K, *modes, cover);
+    if (modes && pb_work) {
+        const dim3 grid((W + CP_TX - 1) / CP_TX, (H + CP_TY - 1) / CP_TY);
+        int rc = pb_clear_report(pb_work, st);
+        if (rc != DGX_OK) return rc;
+        int k0 = 0;
+        bool first = true;
+        for (int k = 0; k <= K; ++k) {
+            if (k < K && modes->m[k] != CP_POISSON) continue;
+            if (first || k > k0)                       // the first launch also writes the cover words, even with nothing to fold
+                hipLaunchKernelGGL(cp_blend_kernel<true>, grid, dim3(CP_TX * CP_TY), 0, st, image, H, W, src_rgba, src_desc, K, *modes,
+                                   cover, k0, k, first ? 1 : 0);
+            first = false;
+            if (k < K) {
+                rc = pb_enqueue(image, H, W, src_rgba, src_desc + 5 * k, PbDesc{}, pb_work, pb_nmax, -1, k, st);
+                if (rc != DGX_OK) return rc;
+            }
+            k0 = k + 1;
+        }
+    } else if (modes) {
+        hipLaunchKernelGGL(cp_blend_kernel<false>, dim3((W + CP_TX - 1) / CP_TX, (H + CP_TY - 1) / CP_TY), dim3(CP_TX * CP_TY), 0, st,
+                           image, H, W, src_rgba, src_desc, K, *modes, cover, 0, K, 1);
     } else {
         const int gp = (int)((HW + 255) / 256 < 4096 ? (HW + 255) / 256 : 4096);
         hipLaunchKernelGGL(cp_cover_blend_kernel, dim3(gp), dim3(256), 0, st, image, H, W, src_rgba, src_desc, K, cover);
@@ -415,4 +443,31 @@ extern "C" int dgx_copy_paste_blend(uint8_t* image, const uint8_t* masks, const 
     if (gaussian && (H < 3 || W < 3)) return DGX_ERR_UNSUPPORTED;     // reflect-101 needs 3 pixels per side
     return cp_launch(image, masks, boxes0, n0, H, W, src_rgba, src_desc, K, out_masks, out_boxes, out_valid, stats,
                      blend ? &modes : nullptr, stream);
+}
+
+extern "C" int dgx_copy_paste_blend_ws(uint8_t* image, const uint8_t* masks, const float* boxes0, int n0, int H, int W,
+                                       const uint8_t* src_rgba, const int32_t* src_desc, int K, uint8_t* out_masks,
+                                       float* out_boxes, uint8_t* out_valid, int32_t* stats, const uint8_t* modes_host,
+                                       void* work, size_t work_bytes, void* stream) {
+    if (K <= 0 || H <= 0 || W <= 0) return K < 0 ? DGX_ERR_BAD_ARG : DGX_OK;
+    const int rc = cp_check_args(image, masks, boxes0, n0, H, W, src_rgba, src_desc, K, out_masks, out_boxes, out_valid, stats);
+    if (rc != DGX_OK) return rc;
+    CpModes modes = {};
+    bool blend = false, gaussian = false, poisson = false;
+    for (int k = 0; modes_host && k < K; ++k) {
+        if (modes_host[k] > CP_POISSON) return DGX_ERR_BAD_ARG;
+        modes.m[k] = modes_host[k];
+        blend = blend || modes_host[k] != CP_BASIC;
+        gaussian = gaussian || modes_host[k] == CP_GAUSSIAN;
+        poisson = poisson || modes_host[k] == CP_POISSON;
+    }
+    if ((gaussian || poisson) && (H < 3 || W < 3)) return DGX_ERR_UNSUPPORTED;
+    int64_t nmax = 0;
+    if (poisson) {
+        if ((int64_t)H * W >= ((int64_t)1 << 31)) return DGX_ERR_UNSUPPORTED;
+        nmax = pb_capacity(H, W, work, work_bytes);
+        if (nmax < 0) return DGX_ERR_BAD_ARG;
+    }
+    return cp_launch(image, masks, boxes0, n0, H, W, src_rgba, src_desc, K, out_masks, out_boxes, out_valid, stats,
+                     blend ? &modes : nullptr, stream, poisson ? work : nullptr, nmax);
 }

@@ -712,6 +712,10 @@ def pack_sample(d):
         # inline, where a tensor would cost the training thread a shared-memory handle round trip.  All 'basic' (the shipped
         # configs): nothing is added, the sample crosses the queue exactly as before.
         out["blob_modes"] = np.ascontiguousarray(modes, dtype=np.uint8)
+        if (out["blob_modes"] == 3).any():
+            # a 'possion' paste (INPUT.CP_POISSON): the compositor sizes the solver's workspace from the paste's rectangle, on the
+            # host -- the K descriptors travel once more next to the modes (they are also in the blob, for the device)
+            out["blob_desc"] = np.ascontiguousarray(d["paste_pack"]["desc"].numpy(), dtype=np.int32).reshape(-1, 5)
     extra = {k: v for k, v in d["instances"].get_fields().items() if k not in ("gt_masks", "gt_boxes", "gt_classes")}
     if extra:
         out["blob_extra_fields"] = extra
@@ -745,6 +749,8 @@ def unpack_sample(d, device, ring=None):
         out["paste_pack"] = {"flat": f["flat"], "desc": f["desc"], "labels": f["labels"], "K": d["blob_K"]}
         if d.get("blob_modes") is not None:
             out["paste_pack"]["modes"] = d["blob_modes"]
+        if d.get("blob_desc") is not None:
+            out["paste_pack"]["desc_host"] = d["blob_desc"]
     if "scp_image" in f:
         out["scp_src"] = {"image": f["scp_image"], "masks": f["scp_masks"], "boxes": f["scp_boxes"], "labels": f["scp_labels"],
                           "hw": tuple(d["blob_scp_hw"])}

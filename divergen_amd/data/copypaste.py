@@ -14,7 +14,10 @@ the rest), random placement.  Two halves:
   InstPool.composite  training process: upload + ONE call into libdgx (dgx_copy_paste, or dgx_copy_paste_blend when a paste is
                       not 'basic') for the pixels -- image blend, mask occlusion updates, box recomputation and the occlusion
                       filter of `_copy_paste`, all pastes at once.
-'possion' (Poisson blending, a sparse solve over all H*W pixels per channel per paste) is not built: from_config refuses it."""
+'possion' (Poisson blending, a sparse solve per channel per paste) is opt-in: this build's key INPUT.CP_POISSON (default false)
+admits it to INPUT.CP_METHOD; without the key from_config refuses it.  With it a 'possion' paste is one conjugate-gradient solve on
+the device (dgx_copy_paste_blend_ws, csrc/poisson_blend.hip), it rewrites the image frame as the reference's poisson_edit does, and
+composite() leaves the solver report unread (layers.copy_paste.check_poisson_report reads one)."""
 import json
 import os
 import random
@@ -23,16 +26,19 @@ from collections import defaultdict
 import numpy as np
 import torch
 
-from ..layers.copy_paste import BLEND_MODES, PackedPastes, copy_paste
+from ..layers.copy_paste import BLEND_MODES, BLEND_MODES_ALL, PackedPastes, copy_paste
 from ..structures import BitMasks, Boxes, Instances
 
 
-def check_cp_method(cp_method):
-    """INPUT.CP_METHOD -> list of mode names; every name must be a built blend mode (layers.copy_paste.BLEND_MODES)."""
+def check_cp_method(cp_method, allow_poisson=False):
+    """INPUT.CP_METHOD -> list of mode names; every name must be a built blend mode (layers.copy_paste.BLEND_MODES), or 'possion'
+    when allow_poisson (INPUT.CP_POISSON) says so."""
     names = [cp_method] if isinstance(cp_method, str) else list(cp_method)
     if not names:
         raise ValueError("INPUT.CP_METHOD is empty: name at least one of %s" % sorted(BLEND_MODES))
     for n in names:
+        if n == "possion" and allow_poisson:
+            continue
         if n == "possion":
             raise NotImplementedError("INPUT.CP_METHOD 'possion' is not built: the reference solves a sparse system over all H*W "
                                       "pixels per channel per paste (spsolve), which needs a GPU solver of its own")
@@ -55,7 +61,7 @@ class InstPool:
     def __init__(self, pool_json, train_size, area_stats_json=None, max_samples=20, random_scale=False,
                  random_scale_min=0.1, random_scale_max=2.0, random_scale_min_size=5, use_largest_part=True,
                  scale_min=10, scale_max=0.5, shape_jitter=0.2, mask_threshold=128,
-                 instance_filter_min=0.01, instance_filter_max=1.0, loader=None, cp_method=("basic",)):
+                 instance_filter_min=0.01, instance_filter_max=1.0, loader=None, cp_method=("basic",), allow_poisson=False):
         pool = json.load(open(pool_json)) if isinstance(pool_json, str) else pool_json
         self.per_cat_pool = defaultdict(list)
         self.dataset, self.data_to_cat = [], {}
@@ -73,7 +79,8 @@ class InstPool:
         self.shape_jitter, self.mask_threshold = shape_jitter, mask_threshold
         self.filter_min, self.filter_max = instance_filter_min, instance_filter_max
         self.loader = loader or self._pil_loader
-        self.cp_method = check_cp_method(cp_method)
+        self.allow_poisson = bool(allow_poisson)
+        self.cp_method = check_cp_method(cp_method, self.allow_poisson)
         self.rng = random.Random()        # blend-mode draws only (seed: the loader's _worker_init); never the global `random`
 
     def seed(self, seed):
@@ -85,7 +92,7 @@ class InstPool:
         """The constructor call of CopyPasteMapper.from_config (mapper.py:726-745) for INST_POOL_FORMAT 'RGBA', including
         the category filter of InstPool.__init__ (:115-133: keep pool categories whose LVIS frequency is in INST_POOL_FREQ).
         INPUT.INST_POOL_SHARDS (this build's key) switches the per-sample decode to the shard store.  INPUT.CP_METHOD is checked
-        here: 'possion' and unknown names raise NotImplementedError."""
+        here: unknown names raise NotImplementedError, and so does 'possion' unless INPUT.CP_POISSON (this build's key) is true."""
         with open(cfg.INPUT.INST_POOL_PATH) as f:
             pool = json.load(f)
         freq_path = cfg.MODEL.ROI_BOX_HEAD.CAT_FREQ_PATH
@@ -102,7 +109,7 @@ class InstPool:
                    max_samples=cfg.INPUT.INST_POOL_MAX_SAMPLES, random_scale=cfg.INPUT.RANDOM_SCALE,
                    random_scale_min=cfg.INPUT.RANDOM_SCALE_MIN, random_scale_max=cfg.INPUT.RANDOM_SCALE_MAX,
                    random_scale_min_size=cfg.INPUT.RANDOM_SCALE_MIN_SIZE, use_largest_part=cfg.USE_LARGEST_PART, loader=loader,
-                   cp_method=cfg.INPUT.CP_METHOD)
+                   cp_method=cfg.INPUT.CP_METHOD, allow_poisson=bool(cfg.INPUT.get("CP_POISSON", False)))
 
     @staticmethod
     def _pil_loader(path):
@@ -213,7 +220,7 @@ class InstPool:
         albumentations Compose that every loaded patch passes through first (mapper.py:496, `cumstom_augmentations`, empty
         unless INPUT.COLOR_AUG): whether that draws from the global `random`, and how often, depends on the albumentations
         version, which the reference does not pin.  Those draws are not replayed here; the per-paste distribution is the same."""
-        return np.array([BLEND_MODES[self.rng.sample(self.cp_method, 1)[0]] for _ in range(K)], dtype=np.uint8)
+        return np.array([BLEND_MODES_ALL[self.rng.sample(self.cp_method, 1)[0]] for _ in range(K)], dtype=np.uint8)
 
     def prepare(self, data):
         """Loader-worker half of get_mix_result: draw + decode + clean + resize + flip + place + pack.  Adds to the mapped sample
@@ -241,8 +248,14 @@ class InstPool:
         up = lambda t: t.to(device, non_blocking=True)     # noqa: E731
         image, gm = up(data["image"]), up(inst.gt_masks.tensor.view(torch.uint8))
         gb, gc = up(inst.gt_boxes.tensor), up(inst.gt_classes)
-        packed = PackedPastes(up(pk["flat"]), up(pk["desc"]), up(pk["labels"]), int(pk["K"]), pk.get("modes"))      # modes stay on the host
-        out = copy_paste(image, gm, gb, gc, packed, lazy_masks=True)
+        modes = pk.get("modes")
+        poisson = modes is not None and bool((np.asarray(modes) == BLEND_MODES_ALL["possion"]).any())
+        # modes stay on the host; so do the descriptors of a pack with a 'possion' paste (its workspace is sized from them)
+        desc_host = pk.get("desc_host")
+        if desc_host is None and poisson and not pk["desc"].is_cuda:
+            desc_host = pk["desc"].numpy()
+        packed = PackedPastes(up(pk["flat"]), up(pk["desc"]), up(pk["labels"]), int(pk["K"]), modes, desc_host)
+        out = copy_paste(image, gm, gb, gc, packed, lazy_masks=True, allow_poisson=poisson)      # the solver report stays unread
         ni = Instances((H, W))
         ni.gt_boxes, ni.gt_classes = Boxes(out["boxes"]), out["labels"]
         ni.gt_masks, ni.instance_source = BitMasks(out["masks"].view(torch.bool), index=out["keep"]), out["source"]      # 0/1 bytes: a view; rows through the index

@@ -8,11 +8,14 @@ from ..utils.h2d import upload_i32
 
 
 BLEND_MODES = {"basic": 0, "alpha": 1, "gaussian": 2}      # the mode bytes of dgx_copy_paste_blend (include/divergen_hip.h)
+BLEND_MODES_ALL = {**BLEND_MODES, "possion": 3}            # + the opt-in Poisson blend (the reference's spelling): dgx_copy_paste_blend_ws
+POISSON = BLEND_MODES_ALL["possion"]
 
 
-def host_modes(modes, K):
+def host_modes(modes, K, allow_poisson=False):
     """modes (None | sequence of names or codes | uint8 array / CPU tensor) -> uint8 numpy (K,) in host memory, or None when every
-    paste is 'basic' (then the compositor launches exactly the kernels of dgx_copy_paste)."""
+    paste is 'basic' (then the compositor launches exactly the kernels of dgx_copy_paste).  allow_poisson: 'possion' / code 3 pass."""
+    table = BLEND_MODES_ALL if allow_poisson else BLEND_MODES
     if modes is None:
         return None
     if isinstance(modes, torch.Tensor):
@@ -24,23 +27,25 @@ def host_modes(modes, K):
     else:
         vals = list(modes)            # element by element: a mixed list of names and codes keeps its codes
     for v in vals:
-        if isinstance(v, str) and v not in BLEND_MODES:
-            raise ValueError("copy_paste: unknown blend mode '%s' (%s)" % (v, ", ".join(sorted(BLEND_MODES))))
-    m = np.array([BLEND_MODES[v] if isinstance(v, str) else int(v) for v in vals], dtype=np.int64)
+        if isinstance(v, str) and v not in table:
+            raise ValueError("copy_paste: unknown blend mode '%s' (%s)" % (v, ", ".join(sorted(table))))
+    m = np.array([table[v] if isinstance(v, str) else int(v) for v in vals], dtype=np.int64)
     if m.shape[0] != K:
         raise ValueError("copy_paste: %d blend modes for %d pastes" % (m.shape[0], K))
-    if ((m < 0) | (m > 2)).any():
-        raise ValueError("copy_paste: blend mode codes are 0 (basic), 1 (alpha), 2 (gaussian); got %s" % m.tolist())
+    if ((m < 0) | (m > (3 if allow_poisson else 2))).any():
+        raise ValueError("copy_paste: blend mode codes are 0 (basic), 1 (alpha), 2 (gaussian)%s; got %s"
+                         % (", 3 (possion)" if allow_poisson else "", m.tolist()))
     return m.astype(np.uint8) if m.any() else None
 
 
 class PackedPastes:
     """The K paste patches of one image as the kernel takes them: ONE flat uint8 buffer (each RGBA patch padded to 4 bytes) + the
     (K, 5) int32 descriptors (byte offset, h, w, x0, y0) + the K labels, all on the device; `modes`: the K blend-mode bytes
-    (BLEND_MODES) in HOST memory, None = all 'basic'."""
+    (BLEND_MODES) in HOST memory, None = all 'basic'; `desc_host`: the descriptors once more as a host int32 array (K, 5) when the
+    packer had them there (only a 'possion' paste needs them: its workspace is sized from the paste's rectangle), else None."""
 
-    def __init__(self, flat, desc, labels, K, modes=None):
-        self.flat, self.desc, self.labels, self.K, self.modes = flat, desc, labels, K, modes
+    def __init__(self, flat, desc, labels, K, modes=None, desc_host=None):
+        self.flat, self.desc, self.labels, self.K, self.modes, self.desc_host = flat, desc, labels, K, modes, desc_host
 
     def __len__(self):
         return self.K
@@ -64,12 +69,14 @@ def pack_pastes_host(pastes):
     return torch.from_numpy(host), torch.from_numpy(np.asarray(desc, dtype=np.int32).reshape(-1, 5)), torch.from_numpy(labels)
 
 
-def pack_pastes(pastes, device, modes=None):
-    """modes: K blend modes (names or BLEND_MODES codes), None = all 'basic'.  list of (rgba uint8 (h, w, 4) numpy | tensor, x0, y0, label) -> PackedPastes.  Host arrays (the loader's case: patches come
+def pack_pastes(pastes, device, modes=None, allow_poisson=False):
+    """allow_poisson: `modes` may name 'possion' (checked here, so that a wrong name fails where it is given).  modes: K blend modes (names or BLEND_MODES codes), None = all 'basic'.  list of (rgba uint8 (h, w, 4) numpy | tensor, x0, y0, label) -> PackedPastes.  Host arrays (the loader's case: patches come
     out of the instance pool in host memory) are laid out in one host buffer and go up in ONE copy; patches that already live on
     the device are gathered with one concatenation.  Round 2 concatenated 2 K device chunks per image inside every step, which
     torch executes as one hipMemcpyAsync per chunk: 38 blit launches of ~10 us per image (0.8 ms per step on the loader stream)."""
     K = len(pastes)
+    if modes is not None:
+        host_modes(modes, K, allow_poisson)
     on_dev = [isinstance(r, torch.Tensor) and r.is_cuda for r, _, _, _ in pastes]
     if K and all(on_dev):
         desc, off, chunks = [], 0, []
@@ -84,17 +91,40 @@ def pack_pastes(pastes, device, modes=None):
         flat = torch.cat(chunks)
         desc_t = upload_i32(desc, device).view(-1, 5)
         labels = upload_i32([int(np.asarray(p[3]).reshape(-1)[0]) for p in pastes], device).long()
-        return PackedPastes(flat, desc_t, labels, K, modes)
+        return PackedPastes(flat, desc_t, labels, K, modes, np.asarray(desc, dtype=np.int32).reshape(-1, 5))
     flat, desc, labels = pack_pastes_host(pastes)
+    desc_host = desc.numpy().copy()
     if torch.device(device).type != "cuda":
-        return PackedPastes(flat, desc, labels, K, modes)
+        return PackedPastes(flat, desc, labels, K, modes, desc_host)
     flat = flat.pin_memory().to(device, non_blocking=True)
     desc_t = upload_i32(desc.numpy(), device).view(-1, 5) if K else torch.zeros(0, 5, dtype=torch.int32, device=device)
     labels = upload_i32(labels.numpy(), device).long() if K else torch.zeros(0, dtype=torch.int64, device=device)
-    return PackedPastes(flat, desc_t, labels, K, modes)
+    return PackedPastes(flat, desc_t, labels, K, modes, desc_host)
 
 
-def copy_paste(image, masks, boxes, labels, pastes, lazy_masks=False, modes=None):
+def poisson_unknowns(desc_host, H, W):
+    """Upper bound of |U| = |F| + frame for one paste descriptor (offset, h, w, x0, y0): the pixels of its rectangle inside the image
+    plus the image frame, at most H * W."""
+    _, h, w, x0, y0 = (int(v) for v in desc_host)
+    ch, cw = min(y0 + h, H) - max(y0, 0), min(x0 + w, W) - max(x0, 0)
+    return min(H * W, 2 * H + 2 * W - 4 + (ch * cw if ch > 0 and cw > 0 else 0))
+
+
+def check_poisson_report(report, modes=None):
+    """Read the solver report of copy_paste(..., allow_poisson=True) (a device -> host copy: not for the training path) and raise
+    when a 'possion' paste did not converge within its iteration bound.  report: float64 (K, 4) = (iterations, ||r||_2, converged,
+    |U|) per paste, zeros for pastes of other modes; modes: the K mode bytes (None: every paste with a non-zero row is checked).
+    Returns the report as a numpy array."""
+    rep = report.detach().cpu().numpy() if isinstance(report, torch.Tensor) else np.asarray(report)
+    for k, (iters, resid, flag, n) in enumerate(rep.tolist()):
+        solved = int(modes[k]) == POISSON if modes is not None else (n > 0 or iters > 0 or resid != 0)
+        if solved and flag != 1.0:
+            raise RuntimeError("copy_paste: the 'possion' solve of paste %d did not converge: %d iterations, |r| = %.3e, %d unknowns"
+                               % (k, int(iters), resid, int(n)))
+    return rep
+
+
+def copy_paste(image, masks, boxes, labels, pastes, lazy_masks=False, modes=None, allow_poisson=False):
     """image uint8 (3,H,W), masks uint8 (n,H,W), boxes f32 (n,4), labels i64 (n) -- GPU tensors.
     pastes: list of (rgba uint8 numpy/tensor (h,w,4), x0, y0, label) applied in order, or a PackedPastes (pack_pastes).
     Returns dict(image, masks, boxes, labels, source) exactly like the sequential reference.  Mask bytes pass through (0/1 in,
@@ -102,7 +132,10 @@ def copy_paste(image, masks, boxes, labels, pastes, lazy_masks=False, modes=None
     what structures.BitMasks(masks, index=keep) takes: the full-resolution rows of the survivors are then never gathered
     (the only consumer, crop_and_resize, reads a few rows through the index).
     modes: the K blend modes (names or BLEND_MODES codes, host memory); None takes the PackedPastes' own (None there = all 'basic').
-    All 'basic' calls dgx_copy_paste; any other mix dgx_copy_paste_blend.  Masks / boxes / labels / source do not depend on them."""
+    All 'basic' calls dgx_copy_paste; any other mix dgx_copy_paste_blend.  Masks / boxes / labels / source do not depend on them.
+    allow_poisson: 'possion' / code 3 is accepted; with such a paste present the call is dgx_copy_paste_blend_ws with a workspace
+    sized for the largest of them, and the result carries `poisson_report`, float64 (K, 4) on the device (check_poisson_report
+    reads it; nothing here does).  A pack without host descriptors costs one device -> host copy of them."""
     K = len(pastes)
     dev = image.device
     n0, H, W = masks.shape[0], image.shape[1], image.shape[2]
@@ -112,7 +145,7 @@ def copy_paste(image, masks, boxes, labels, pastes, lazy_masks=False, modes=None
             out["keep"] = torch.arange(n0, dtype=torch.int64, device=dev)
         return out
     pk = pastes if isinstance(pastes, PackedPastes) else pack_pastes(pastes, dev)
-    hm = host_modes(modes if modes is not None else pk.modes, K)
+    hm = host_modes(modes if modes is not None else pk.modes, K, allow_poisson)
     flat, desc_t = pk.flat, pk.desc
     image = image.contiguous().clone()
     masks = masks.contiguous()
@@ -122,7 +155,17 @@ def copy_paste(image, masks, boxes, labels, pastes, lazy_masks=False, modes=None
     out_boxes = torch.empty(nobj, 4, dtype=torch.float32, device=dev)
     out_valid = torch.empty(nobj, dtype=torch.uint8, device=dev)
     stats = torch.empty(nobj * (K + 1) * 5 + 3 + H * W, dtype=torch.int32, device=dev)
-    if hm is None:
+    report = None
+    if hm is not None and (hm == POISSON).any():
+        dh = pk.desc_host if getattr(pk, "desc_host", None) is not None else pk.desc.cpu().numpy()
+        nmax = max(poisson_unknowns(dh[k], H, W) for k in np.flatnonzero(hm == POISSON))
+        nbytes = int(L.lib().dgx_poisson_work_bytes(H, W, nmax))
+        work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+        L.check(L.lib().dgx_copy_paste_blend_ws(L.ptr(image), L.ptr(masks) if n0 else None, L.ptr(boxes0) if n0 else None, n0, H, W,
+                                                L.ptr(flat), L.ptr(desc_t), K, L.ptr(out_masks), L.ptr(out_boxes), L.ptr(out_valid),
+                                                L.ptr(stats), hm.ctypes.data, L.ptr(work), nbytes, L.stream()), "dgx_copy_paste_blend_ws")
+        report = work[:4 * 32].view(32, 4)[:K]
+    elif hm is None:
         L.check(L.lib().dgx_copy_paste(L.ptr(image), L.ptr(masks) if n0 else None, L.ptr(boxes0) if n0 else None, n0, H, W,
                                        L.ptr(flat), L.ptr(desc_t), K, L.ptr(out_masks), L.ptr(out_boxes), L.ptr(out_valid),
                                        L.ptr(stats), L.stream()), "dgx_copy_paste")
@@ -138,7 +181,24 @@ def copy_paste(image, masks, boxes, labels, pastes, lazy_masks=False, modes=None
         out["masks"], out["keep"] = out_masks, keep
     else:
         out["masks"] = out_masks.index_select(0, keep)
+    if report is not None:
+        out["poisson_report"] = report
     return out
+
+
+def poisson_blend(image, rgba, x0, y0, max_iter=-1):
+    """ONE 'possion' paste (dgx_poisson_blend) on a copy of image uint8 (3,H,W) (GPU tensor); rgba uint8 (h,w,4) numpy / tensor.
+    Returns (image, report float64 (4,) on the device = (iterations, ||r||_2, converged, |U|)).  max_iter < 0: the library's bound."""
+    dev = image.device
+    H, W = int(image.shape[1]), int(image.shape[2])
+    pk = pack_pastes([(rgba, x0, y0, 0)], dev)
+    d = np.ascontiguousarray(pk.desc_host[0], dtype=np.int32)
+    nbytes = int(L.lib().dgx_poisson_work_bytes(H, W, poisson_unknowns(d, H, W)))
+    work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    image = image.contiguous().clone()
+    L.check(L.lib().dgx_poisson_blend(L.ptr(image), L.ptr(pk.flat), d.ctypes.data, H, W, L.ptr(work), nbytes, int(max_iter),
+                                      L.stream()), "dgx_poisson_blend")
+    return image, work[:4]
 
 
 SELF_COPY_MAX = 99      # dgx_self_copy_paste: m <= 99 (the reference draws m < min(ns + 1, 100))

@@ -325,10 +325,58 @@ int dgx_copy_paste(uint8_t* image, const uint8_t* masks, const float* boxes0, in
  *              H x W mask; m = (float)((double)count * (1.0 / 25));  D' = trunc(fl(fl(D * (1 - m)) + fl(S_k * m))).  The blend
  *              reaches 2 px outside the footprint (background RGB inside the rectangle, black outside it), as the reference's.
  * Masks, boxes and out_valid do not depend on the modes.  A mode byte above 2 -> DGX_ERR_BAD_ARG; a 'gaussian' paste on an
- * image with H < 3 or W < 3 -> DGX_ERR_UNSUPPORTED (reflect-101 is not defined there).  'possion' is not built. */
+ * image with H < 3 or W < 3 -> DGX_ERR_UNSUPPORTED (reflect-101 is not defined there).  'possion' (mode byte 3) needs a
+ * workspace: dgx_copy_paste_blend_ws below; here it is a mode byte above 2. */
 int dgx_copy_paste_blend(uint8_t* image, const uint8_t* masks, const float* boxes0, int n0, int H, int W,
                          const uint8_t* src_rgba, const int32_t* src_desc, int K, uint8_t* out_masks,
                          float* out_boxes, uint8_t* out_valid, int32_t* stats, const uint8_t* modes_host, void* stream);
+
+/* 'possion' blend (the reference's spelling): poisson_edit(source, target, mask) of
+ * DG/divergen/data/transforms/possion_blending.py:27-64 as blend_image calls it per paste (custom_cp_method.py:19-22), ONE paste on an
+ * image in place.  S = the placed RGB of the paste (0 outside its rectangle, alpha-0 pixels inside it included), T = the image the
+ * previous paste left, F = placed alpha > 0.  Per channel, in fp64, over the pixels k = x + y * W:
+ *   interior pixel outside F (1 <= y <= H-2, 1 <= x <= W-2, not in F):  x_k = T_k
+ *   every other pixel -- all of F AND all of the 1-pixel image frame (y in {0, H-1} or x in {0, W-1}), whatever its mask:
+ *       4 x_k - sum(x_j over the 4-neighbours j inside the image) = b_k,
+ *       b_k = 4 S_k - sum(S_j over the neighbours inside the image) in F,  b_k = T_k outside F.
+ *   then clamp to [0, 255], truncate to uint8, all three channels.
+ * The frame rows are the reference's own quirk (its loop that turns rows into identity rows never visits the frame): a 'possion'
+ * paste rewrites nearly every byte of the image frame, footprint or not, even when the footprint is empty.  It is built as the
+ * reference has it.  The unknowns are U = F + frame; bytes outside U are not touched.  The reduced matrix over U (diagonal 4, -1
+ * between neighbouring unknowns, known neighbours on the right-hand side as +T_j) is symmetric positive definite; the solver is
+ * conjugate gradients with all of its state in fp64.
+ * Accuracy: with x* the exact solution, the device solution is within DELTA = 1e-3 grey levels of x* before the clamp (stop at
+ * ||r||_2 <= 0.25e-3 * lambda_min of the H x W Dirichlet Laplacian, a lower bound of the matrix's own).  The reference's sparse LU
+ * is itself not reproducible to the byte by another solver (it returns T - eps on identity rows, then truncates).
+ * Bounded work: 2 * max_iter + 7 kernel launches per paste, nothing read back, no device-side waiting between workgroups;
+ * max_iter < 0 takes dgx_poisson_max_iter(H, W, |U| bound).  A channel that converges earlier makes the remaining launches empty.
+ *   desc_host  5 ints in HOST memory (byte offset into src_rgba, h, w, x0, y0); x0, y0 may be negative or overhang, as in
+ *              dgx_copy_paste.  An empty footprint still solves the frame.
+ *   work       16-byte aligned, at least dgx_poisson_work_bytes(H, W, n) bytes with n >= (pixels of the rectangle inside the image)
+ *              + dgx_poisson_frame_unknowns(H, W), else DGX_ERR_BAD_ARG with nothing launched.
+ *   report     the first 32 records of 4 doubles in `work`; this call writes record 0 = (iterations used, final ||r||_2 as fp64,
+ *              converged 1.0 / 0.0, |U|), the maxima / conjunction over the three channels.  At the cap the flag is 0 and the image
+ *              holds the last iterate.
+ * H < 3 or W < 3 -> DGX_ERR_UNSUPPORTED. */
+int dgx_poisson_blend(uint8_t* image, const uint8_t* src_rgba, const int32_t* desc_host, int H, int W, void* work,
+                      size_t work_bytes, int max_iter, void* stream);
+/* Workspace bytes for up to max_unknowns unknowns (capped at H * W); number of frame pixels; the iteration bound
+ * 100 + 16 * ceil(sqrt(max_unknowns - frame)) (derivation: csrc/poisson_blend.hip). */
+int64_t dgx_poisson_work_bytes(int H, int W, int64_t max_unknowns);
+int64_t dgx_poisson_frame_unknowns(int H, int W);
+int dgx_poisson_max_iter(int H, int W, int64_t max_unknowns);
+/* dgx_copy_paste_blend with a workspace: mode bytes 0..3, 3 = 'possion'.  Without a mode-3 paste it is dgx_copy_paste_blend (the same
+ * kernels, `work` unused and may be NULL).  A mode-3 paste k folds the image with the solve above at its place in the order 0..K-1
+ * (the pastes before it are folded first, the pastes after it see its result) and writes report record k; the records of the other
+ * pastes are zero.  Masks, boxes and out_valid do not depend on the modes.  The descriptors live in device memory, so the solver's
+ * capacity is what fits into `work` and the iteration bound follows from that capacity: size it with dgx_poisson_work_bytes for the
+ * largest mode-3 paste.  A workspace that cannot hold even the frame (or NULL / misaligned) -> DGX_ERR_BAD_ARG with nothing
+ * launched; a paste whose |U| exceeds the capacity is left unblended with flag 0.  H < 3 or W < 3 with a mode-3 paste ->
+ * DGX_ERR_UNSUPPORTED; a mode byte above 3 -> DGX_ERR_BAD_ARG. */
+int dgx_copy_paste_blend_ws(uint8_t* image, const uint8_t* masks, const float* boxes0, int n0, int H, int W,
+                            const uint8_t* src_rgba, const int32_t* src_desc, int K, uint8_t* out_masks,
+                            float* out_boxes, uint8_t* out_valid, int32_t* stats, const uint8_t* modes_host,
+                            void* work, size_t work_bytes, void* stream);
 
 /* Self copy-paste: Simple Copy-Paste between two real images (INPUT.USE_COPY_METHOD 'self_copy' / 'both' / 'p:<f>'), ONE paste step
  * of m selected full-frame instance masks of a source image onto a destination, 'basic' blend.  Replaces the numpy passes of
