@@ -358,7 +358,7 @@ __global__ __launch_bounds__(CP_TX * CP_TY) void cp_blend_kernel(uint8_t* __rest
 // 'possion' ones by cp_blend_kernel<true>, each 'possion' paste by the solver of poisson_blend.hip, in the order 0..K-1.
 static int cp_launch(uint8_t* image, const uint8_t* masks, const float* boxes0, int n0, int H, int W, const uint8_t* src_rgba,
                      const int32_t* src_desc, int K, uint8_t* out_masks, float* out_boxes, uint8_t* out_valid, int32_t* stats,
-                     const CpModes* modes, void* stream, void* pb_work = nullptr, int64_t pb_nmax = 0) {
+                     const CpModes* modes, void* pb_work, int64_t pb_nmax, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     // cover words live at the tail of the stats workspace: (n0+K)*(K+1)*5 ints, rounded up to a 16-byte boundary, then H*W words
     const int64_t ns = (int64_t)(n0 + K) * (K + 1) * 5;
@@ -366,8 +366,8 @@ static int cp_launch(uint8_t* image, const uint8_t* masks, const float* boxes0, 
     uint32_t* cover = reinterpret_cast<uint32_t*>(stats + ((ns + 3) & ~(int64_t)3));
     const int64_t HW = (int64_t)H * W;
     hipLaunchKernelGGL(cp_stats_init_kernel, dim3((int)((ns + 255) / 256)), dim3(256), 0, st, stats, ns);
+    const dim3 tiles((W + CP_TX - 1) / CP_TX, (H + CP_TY - 1) / CP_TY);      // the grid of cp_blend_kernel
     if (modes && pb_work) {
-        const dim3 grid((W + CP_TX - 1) / CP_TX, (H + CP_TY - 1) / CP_TY);
         int rc = pb_clear_report(pb_work, st);
         if (rc != DGX_OK) return rc;
         int k0 = 0;
@@ -375,7 +375,7 @@ static int cp_launch(uint8_t* image, const uint8_t* masks, const float* boxes0, 
         for (int k = 0; k <= K; ++k) {
             if (k < K && modes->m[k] != CP_POISSON) continue;
             if (first || k > k0)                       // the first launch also writes the cover words, even with nothing to fold
-                hipLaunchKernelGGL(cp_blend_kernel<true>, grid, dim3(CP_TX * CP_TY), 0, st, image, H, W, src_rgba, src_desc, K, *modes,
+                hipLaunchKernelGGL(cp_blend_kernel<true>, tiles, dim3(CP_TX * CP_TY), 0, st, image, H, W, src_rgba, src_desc, K, *modes,
                                    cover, k0, k, first ? 1 : 0);
             first = false;
             if (k < K) {
@@ -385,8 +385,8 @@ static int cp_launch(uint8_t* image, const uint8_t* masks, const float* boxes0, 
             k0 = k + 1;
         }
     } else if (modes) {
-        hipLaunchKernelGGL(cp_blend_kernel<false>, dim3((W + CP_TX - 1) / CP_TX, (H + CP_TY - 1) / CP_TY), dim3(CP_TX * CP_TY), 0, st,
-                           image, H, W, src_rgba, src_desc, K, *modes, cover, 0, K, 1);
+        hipLaunchKernelGGL(cp_blend_kernel<false>, tiles, dim3(CP_TX * CP_TY), 0, st, image, H, W, src_rgba, src_desc, K, *modes, cover,
+                           0, K, 1);
     } else {
         const int gp = (int)((HW + 255) / 256 < 4096 ? (HW + 255) / 256 : 4096);
         hipLaunchKernelGGL(cp_cover_blend_kernel, dim3(gp), dim3(256), 0, st, image, H, W, src_rgba, src_desc, K, cover);
@@ -407,61 +407,26 @@ static int cp_launch(uint8_t* image, const uint8_t* masks, const float* boxes0, 
     return DGX_OK;
 }
 
-static int cp_check_args(uint8_t* image, const uint8_t* masks, const float* boxes0, int n0, int H, int W, const uint8_t* src_rgba,
-                         const int32_t* src_desc, int K, uint8_t* out_masks, float* out_boxes, uint8_t* out_valid, int32_t* stats) {
+// The body of the three entry points, which differ in the highest mode byte they admit (max_mode) and in whether they bring a
+// workspace.  modes_host == nullptr or all CP_BASIC: the 'basic' launch.  The order of the checks is part of the ABI's behaviour.
+static int cp_run(uint8_t* image, const uint8_t* masks, const float* boxes0, int n0, int H, int W, const uint8_t* src_rgba,
+                  const int32_t* src_desc, int K, uint8_t* out_masks, float* out_boxes, uint8_t* out_valid, int32_t* stats,
+                  const uint8_t* modes_host, int max_mode, void* work, size_t work_bytes, void* stream) {
+    if (K <= 0 || H <= 0 || W <= 0) return K < 0 ? DGX_ERR_BAD_ARG : DGX_OK;
     if (K > CP_MAX_K) return DGX_ERR_UNSUPPORTED;
     if (!image || !src_rgba || !src_desc || !out_masks || !out_boxes || !out_valid || !stats || n0 < 0 ||
         (n0 > 0 && (!masks || !boxes0)))
         return DGX_ERR_BAD_ARG;
-    return DGX_OK;
-}
-
-extern "C" int dgx_copy_paste(uint8_t* image, const uint8_t* masks, const float* boxes0, int n0, int H, int W,
-                              const uint8_t* src_rgba, const int32_t* src_desc, int K, uint8_t* out_masks,
-                              float* out_boxes, uint8_t* out_valid, int32_t* stats, void* stream) {
-    if (K <= 0 || H <= 0 || W <= 0) return K < 0 ? DGX_ERR_BAD_ARG : DGX_OK;
-    const int rc = cp_check_args(image, masks, boxes0, n0, H, W, src_rgba, src_desc, K, out_masks, out_boxes, out_valid, stats);
-    if (rc != DGX_OK) return rc;
-    return cp_launch(image, masks, boxes0, n0, H, W, src_rgba, src_desc, K, out_masks, out_boxes, out_valid, stats, nullptr, stream);
-}
-
-extern "C" int dgx_copy_paste_blend(uint8_t* image, const uint8_t* masks, const float* boxes0, int n0, int H, int W,
-                                    const uint8_t* src_rgba, const int32_t* src_desc, int K, uint8_t* out_masks,
-                                    float* out_boxes, uint8_t* out_valid, int32_t* stats, const uint8_t* modes_host,
-                                    void* stream) {
-    if (K <= 0 || H <= 0 || W <= 0) return K < 0 ? DGX_ERR_BAD_ARG : DGX_OK;
-    const int rc = cp_check_args(image, masks, boxes0, n0, H, W, src_rgba, src_desc, K, out_masks, out_boxes, out_valid, stats);
-    if (rc != DGX_OK) return rc;
-    CpModes modes = {};
-    bool blend = false, gaussian = false;
-    for (int k = 0; modes_host && k < K; ++k) {
-        if (modes_host[k] > CP_GAUSSIAN) return DGX_ERR_BAD_ARG;
-        modes.m[k] = modes_host[k];
-        blend = blend || modes_host[k] != CP_BASIC;
-        gaussian = gaussian || modes_host[k] == CP_GAUSSIAN;
-    }
-    if (gaussian && (H < 3 || W < 3)) return DGX_ERR_UNSUPPORTED;     // reflect-101 needs 3 pixels per side
-    return cp_launch(image, masks, boxes0, n0, H, W, src_rgba, src_desc, K, out_masks, out_boxes, out_valid, stats,
-                     blend ? &modes : nullptr, stream);
-}
-
-extern "C" int dgx_copy_paste_blend_ws(uint8_t* image, const uint8_t* masks, const float* boxes0, int n0, int H, int W,
-                                       const uint8_t* src_rgba, const int32_t* src_desc, int K, uint8_t* out_masks,
-                                       float* out_boxes, uint8_t* out_valid, int32_t* stats, const uint8_t* modes_host,
-                                       void* work, size_t work_bytes, void* stream) {
-    if (K <= 0 || H <= 0 || W <= 0) return K < 0 ? DGX_ERR_BAD_ARG : DGX_OK;
-    const int rc = cp_check_args(image, masks, boxes0, n0, H, W, src_rgba, src_desc, K, out_masks, out_boxes, out_valid, stats);
-    if (rc != DGX_OK) return rc;
     CpModes modes = {};
     bool blend = false, gaussian = false, poisson = false;
     for (int k = 0; modes_host && k < K; ++k) {
-        if (modes_host[k] > CP_POISSON) return DGX_ERR_BAD_ARG;
+        if (modes_host[k] > max_mode) return DGX_ERR_BAD_ARG;
         modes.m[k] = modes_host[k];
         blend = blend || modes_host[k] != CP_BASIC;
         gaussian = gaussian || modes_host[k] == CP_GAUSSIAN;
         poisson = poisson || modes_host[k] == CP_POISSON;
     }
-    if ((gaussian || poisson) && (H < 3 || W < 3)) return DGX_ERR_UNSUPPORTED;
+    if ((gaussian || poisson) && (H < 3 || W < 3)) return DGX_ERR_UNSUPPORTED;     // reflect-101 needs 3 pixels per side
     int64_t nmax = 0;
     if (poisson) {
         if ((int64_t)H * W >= ((int64_t)1 << 31)) return DGX_ERR_UNSUPPORTED;
@@ -469,5 +434,28 @@ extern "C" int dgx_copy_paste_blend_ws(uint8_t* image, const uint8_t* masks, con
         if (nmax < 0) return DGX_ERR_BAD_ARG;
     }
     return cp_launch(image, masks, boxes0, n0, H, W, src_rgba, src_desc, K, out_masks, out_boxes, out_valid, stats,
-                     blend ? &modes : nullptr, stream, poisson ? work : nullptr, nmax);
+                     blend ? &modes : nullptr, poisson ? work : nullptr, nmax, stream);
+}
+
+extern "C" int dgx_copy_paste(uint8_t* image, const uint8_t* masks, const float* boxes0, int n0, int H, int W,
+                              const uint8_t* src_rgba, const int32_t* src_desc, int K, uint8_t* out_masks,
+                              float* out_boxes, uint8_t* out_valid, int32_t* stats, void* stream) {
+    return cp_run(image, masks, boxes0, n0, H, W, src_rgba, src_desc, K, out_masks, out_boxes, out_valid, stats, nullptr, CP_BASIC,
+                  nullptr, 0, stream);
+}
+
+extern "C" int dgx_copy_paste_blend(uint8_t* image, const uint8_t* masks, const float* boxes0, int n0, int H, int W,
+                                    const uint8_t* src_rgba, const int32_t* src_desc, int K, uint8_t* out_masks,
+                                    float* out_boxes, uint8_t* out_valid, int32_t* stats, const uint8_t* modes_host,
+                                    void* stream) {
+    return cp_run(image, masks, boxes0, n0, H, W, src_rgba, src_desc, K, out_masks, out_boxes, out_valid, stats, modes_host,
+                  CP_GAUSSIAN, nullptr, 0, stream);
+}
+
+extern "C" int dgx_copy_paste_blend_ws(uint8_t* image, const uint8_t* masks, const float* boxes0, int n0, int H, int W,
+                                       const uint8_t* src_rgba, const int32_t* src_desc, int K, uint8_t* out_masks,
+                                       float* out_boxes, uint8_t* out_valid, int32_t* stats, const uint8_t* modes_host,
+                                       void* work, size_t work_bytes, void* stream) {
+    return cp_run(image, masks, boxes0, n0, H, W, src_rgba, src_desc, K, out_masks, out_boxes, out_valid, stats, modes_host,
+                  CP_POISSON, work, work_bytes, stream);
 }

@@ -621,6 +621,7 @@ class CopyPasteMapper:
         gt_boxes / gt_classes / gt_masks only (custom_copypaste.py:311-318: instance_source and every other field are gone, also
         when nothing was pasted)."""
         from ..layers.copy_paste import self_copy_paste
+        from .copypaste import result_instances
         if dev.type != "cuda":
             raise RuntimeError("INPUT.USE_COPY_METHOD with a self copy needs the GPU compositor (dgx_self_copy_paste); device is %s" % dev)
         inst = out["instances"]
@@ -629,10 +630,8 @@ class CopyPasteMapper:
         r = self_copy_paste(out["image"], inst.gt_masks.tensor.view(torch.uint8), inst.gt_boxes.tensor, inst.gt_classes,
                             up(scp["image"]), up(scp["masks"]), up(scp["boxes"]), up(scp["labels"]), np.arange(m),
                             canvas_hw=scp["hw"], lazy_masks=True)
-        H, W = (int(v) for v in r["image"].shape[-2:])
-        out["image"], out["height"], out["width"] = r["image"], H, W
-        out["instances"] = Instances((H, W), gt_boxes=Boxes(r["boxes"]), gt_classes=r["labels"],
-                                     gt_masks=BitMasks(r["masks"].view(torch.bool), index=r["keep"]))
+        out["instances"] = result_instances(r, with_source=False)
+        out["image"], (out["height"], out["width"]) = r["image"], out["instances"].image_size
         return out
 
     def finish(self, result, device):
@@ -711,8 +710,9 @@ def pack_sample(d):
         # K blend-mode bytes, read by the host when it launches the compositor (so not in the blob), as a numpy array: it pickles
         # inline, where a tensor would cost the training thread a shared-memory handle round trip.  All 'basic' (the shipped
         # configs): nothing is added, the sample crosses the queue exactly as before.
+        from ..layers.copy_paste import POISSON
         out["blob_modes"] = np.ascontiguousarray(modes, dtype=np.uint8)
-        if (out["blob_modes"] == 3).any():
+        if (out["blob_modes"] == POISSON).any():
             # a 'possion' paste (INPUT.CP_POISSON): the compositor sizes the solver's workspace from the paste's rectangle, on the
             # host -- the K descriptors travel once more next to the modes (they are also in the blob, for the device)
             out["blob_desc"] = np.ascontiguousarray(d["paste_pack"]["desc"].numpy(), dtype=np.int32).reshape(-1, 5)

@@ -1,23 +1,25 @@
 """DiverGen copy-paste data path with the GPU compositor.
 
 Host-side mirror of InstPool (DG/divergen/data/custom_build_copypaste_mapper.py:94-566) for the shipped
-configuration (INST_POOL_FORMAT 'RGBA', INST_POOL_SAMPLE_TYPE 'cas_random', USE_COPY_METHOD 'syn_copy') with the blend modes
-'basic', 'alpha' and 'gaussian' of INPUT.CP_METHOD (custom_cp_method.py:5-18): class-balanced sampling of generated instances, size prior (Gaussian
-relative-area prior for LVIS classes with statistics, U(RANDOM_SCALE_MIN, MAX) of the source size for
-the rest), random placement.  Two halves:
+configuration (INST_POOL_FORMAT 'RGBA', INST_POOL_SAMPLE_TYPE 'cas_random', USE_COPY_METHOD 'syn_copy'): class-balanced sampling
+of generated instances, size prior (Gaussian relative-area prior for LVIS classes with statistics, U(RANDOM_SCALE_MIN, MAX) of
+the source size for the rest), random placement.  The four blend modes of INPUT.CP_METHOD (custom_cp_method.py:5-18):
+  'basic', 'alpha', 'gaussian'   always built; per pixel, folded over the K pastes in one kernel
+  'possion'                      Poisson blending (the reference's spelling), opt-in: this build's key INPUT.CP_POISSON (default false) admits
+                                 it, without the key from_config refuses it.  One conjugate-gradient solve per paste on the device
+                                 (csrc/poisson_blend.hip); it rewrites the image frame as the reference's poisson_edit does; composite()
+                                 leaves the solver report unread (layers.copy_paste.check_poisson_report reads one)
+Two halves:
   InstPool.prepare    numpy / PIL only, the reference's np.random call order (pinned on tests/golden/pool_draws.npz, draws of
                       the reference's own InstPool); runs in the DATALOADER.NUM_WORKERS loader processes and returns the K
                       patches packed into one flat buffer + descriptors (CPU tensors) + one blend mode per paste, drawn like
                       blend_image's `random.sample(cp_method, 1)[0]` from the pool's OWN random.Random (seeded by the loader's
                       _worker_init with the worker's seed, as D2's seed_all_rng seeds `random`; the process's global `random`
                       and the np.random stream are not touched)
-  InstPool.composite  training process: upload + ONE call into libdgx (dgx_copy_paste, or dgx_copy_paste_blend when a paste is
-                      not 'basic') for the pixels -- image blend, mask occlusion updates, box recomputation and the occlusion
-                      filter of `_copy_paste`, all pastes at once.
-'possion' (Poisson blending, a sparse solve per channel per paste) is opt-in: this build's key INPUT.CP_POISSON (default false)
-admits it to INPUT.CP_METHOD; without the key from_config refuses it.  With it a 'possion' paste is one conjugate-gradient solve on
-the device (dgx_copy_paste_blend_ws, csrc/poisson_blend.hip), it rewrites the image frame as the reference's poisson_edit does, and
-composite() leaves the solver report unread (layers.copy_paste.check_poisson_report reads one)."""
+  InstPool.composite  training process: upload + ONE call into libdgx (layers.copy_paste.copy_paste picks the entry point from the
+                      modes: dgx_copy_paste, dgx_copy_paste_blend, or dgx_copy_paste_blend_ws with a 'possion' paste) for the
+                      pixels -- image blend, mask occlusion updates, box recomputation and the occlusion filter of
+                      `_copy_paste`, all pastes at once."""
 import json
 import os
 import random
@@ -45,6 +47,16 @@ def check_cp_method(cp_method, allow_poisson=False):
         if n not in BLEND_MODES:
             raise NotImplementedError("INPUT.CP_METHOD '%s' is not a blend mode of this build (%s)" % (n, ", ".join(sorted(BLEND_MODES))))
     return names
+
+
+def result_instances(out, with_source=True):
+    """The result dict of layers.copy_paste.copy_paste / self_copy_paste (lazy_masks=True) -> the Instances of its image: gt_boxes,
+    gt_classes, gt_masks (0/1 bytes: a bool view; the survivors' rows through the index) and, with_source, instance_source."""
+    inst = Instances(tuple(int(v) for v in out["image"].shape[-2:]), gt_boxes=Boxes(out["boxes"]), gt_classes=out["labels"],
+                     gt_masks=BitMasks(out["masks"].view(torch.bool), index=out["keep"]))
+    if with_source:
+        inst.instance_source = out["source"]
+    return inst
 
 
 def largest_connected_component(mask):
@@ -240,7 +252,7 @@ class InstPool:
     @staticmethod
     def composite(data, device):
         """Training-process half: the prepared sample's tensors go to `device` (asynchronously when they are pinned) and ONE
-        dgx_copy_paste(_blend) call on the CURRENT stream blends all K patches, updates masks / boxes and drops covered objects.  The
+        libdgx call (copy_paste) on the CURRENT stream blends all K patches, updates masks / boxes and drops covered objects.  The
         caller chooses the stream (data/build.py: a side stream, one batch ahead of the training stream)."""
         pk = data["paste_pack"]
         inst = data["instances"]
@@ -248,19 +260,12 @@ class InstPool:
         up = lambda t: t.to(device, non_blocking=True)     # noqa: E731
         image, gm = up(data["image"]), up(inst.gt_masks.tensor.view(torch.uint8))
         gb, gc = up(inst.gt_boxes.tensor), up(inst.gt_classes)
-        modes = pk.get("modes")
-        poisson = modes is not None and bool((np.asarray(modes) == BLEND_MODES_ALL["possion"]).any())
-        # modes stay on the host; so do the descriptors of a pack with a 'possion' paste (its workspace is sized from them)
-        desc_host = pk.get("desc_host")
-        if desc_host is None and poisson and not pk["desc"].is_cuda:
-            desc_host = pk["desc"].numpy()
-        packed = PackedPastes(up(pk["flat"]), up(pk["desc"]), up(pk["labels"]), int(pk["K"]), modes, desc_host)
-        out = copy_paste(image, gm, gb, gc, packed, lazy_masks=True, allow_poisson=poisson)      # the solver report stays unread
-        ni = Instances((H, W))
-        ni.gt_boxes, ni.gt_classes = Boxes(out["boxes"]), out["labels"]
-        ni.gt_masks, ni.instance_source = BitMasks(out["masks"].view(torch.bool), index=out["keep"]), out["source"]      # 0/1 bytes: a view; rows through the index
+        # modes stay on the host, and so do the descriptors wherever they already are there (the loader's `desc_host`, a pack not yet uploaded)
+        desc_host = pk.get("desc_host", None if pk["desc"].is_cuda else pk["desc"].numpy())
+        packed = PackedPastes(up(pk["flat"]), up(pk["desc"]), up(pk["labels"]), int(pk["K"]), pk.get("modes"), desc_host)
+        out = copy_paste(image, gm, gb, gc, packed, lazy_masks=True, allow_poisson=True)      # the pool refused 'possion' where it is off
         data = {k: v for k, v in data.items() if k != "paste_pack"}
-        data["image"], data["instances"], data["height"], data["width"] = out["image"], ni, H, W
+        data["image"], data["instances"], data["height"], data["width"] = out["image"], result_instances(out), H, W
         data["_uploaded"] = (image, gm, gb, gc)      # the un-pasted sample on the device (BSGAL keeps it; copy_paste wrote a clone)
         return data
 

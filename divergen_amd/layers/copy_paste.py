@@ -1,5 +1,6 @@
-"""Instance copy-paste compositor ('basic' blend) on the GPU.
-Reference: DG/divergen/data/custom_build_copypaste_mapper.py:488-566, :79-92."""
+"""Instance copy-paste compositor on the GPU: the 'basic', 'alpha', 'gaussian' and (opt-in) 'possion' blends of all K pastes of an
+image in one libdgx call (copy_paste), one 'possion' paste alone (poisson_blend), and the self copy between two real images
+(self_copy_paste).  Reference: DG/divergen/data/custom_build_copypaste_mapper.py:488-566, :79-92; custom_cp_method.py:5-18."""
 import numpy as np
 import torch
 
@@ -10,14 +11,18 @@ from ..utils.h2d import upload_i32
 BLEND_MODES = {"basic": 0, "alpha": 1, "gaussian": 2}      # the mode bytes of dgx_copy_paste_blend (include/divergen_hip.h)
 BLEND_MODES_ALL = {**BLEND_MODES, "possion": 3}            # + the opt-in Poisson blend (the reference's spelling): dgx_copy_paste_blend_ws
 POISSON = BLEND_MODES_ALL["possion"]
+# the solver report at the head of the 'possion' workspace: PB_REPORT_RECORDS records of PB_REPORT_DOUBLES fp64 (csrc/poisson_blend.h)
+POISSON_REPORT_RECORDS = 32
+POISSON_REPORT_FIELDS = 4      # (iterations, ||r||_2, converged, |U|)
 
 
 def host_modes(modes, K, allow_poisson=False):
     """modes (None | sequence of names or codes | uint8 array / CPU tensor) -> uint8 numpy (K,) in host memory, or None when every
     paste is 'basic' (then the compositor launches exactly the kernels of dgx_copy_paste).  allow_poisson: 'possion' / code 3 pass."""
-    table = BLEND_MODES_ALL if allow_poisson else BLEND_MODES
     if modes is None:
         return None
+    top = POISSON if allow_poisson else max(BLEND_MODES.values())      # the highest code admitted
+    admitted = sorted((c, n) for n, c in BLEND_MODES_ALL.items() if c <= top)
     if isinstance(modes, torch.Tensor):
         modes = modes.cpu().numpy()
     if isinstance(modes, np.ndarray):
@@ -27,19 +32,18 @@ def host_modes(modes, K, allow_poisson=False):
     else:
         vals = list(modes)            # element by element: a mixed list of names and codes keeps its codes
     for v in vals:
-        if isinstance(v, str) and v not in table:
-            raise ValueError("copy_paste: unknown blend mode '%s' (%s)" % (v, ", ".join(sorted(table))))
-    m = np.array([table[v] if isinstance(v, str) else int(v) for v in vals], dtype=np.int64)
+        if isinstance(v, str) and BLEND_MODES_ALL.get(v, top + 1) > top:
+            raise ValueError("copy_paste: unknown blend mode '%s' (%s)" % (v, ", ".join(sorted(n for _, n in admitted))))
+    m = np.array([BLEND_MODES_ALL[v] if isinstance(v, str) else int(v) for v in vals], dtype=np.int64)
     if m.shape[0] != K:
         raise ValueError("copy_paste: %d blend modes for %d pastes" % (m.shape[0], K))
-    if ((m < 0) | (m > (3 if allow_poisson else 2))).any():
-        raise ValueError("copy_paste: blend mode codes are 0 (basic), 1 (alpha), 2 (gaussian)%s; got %s"
-                         % (", 3 (possion)" if allow_poisson else "", m.tolist()))
+    if ((m < 0) | (m > top)).any():
+        raise ValueError("copy_paste: blend mode codes are %s; got %s" % (", ".join("%d (%s)" % cn for cn in admitted), m.tolist()))
     return m.astype(np.uint8) if m.any() else None
 
 
 class PackedPastes:
-    """The K paste patches of one image as the kernel takes them: ONE flat uint8 buffer (each RGBA patch padded to 4 bytes) + the
+    """The K paste patches of one image as the kernel takes them: ONE flat uint8 buffer (the RGBA patches back to back) + the
     (K, 5) int32 descriptors (byte offset, h, w, x0, y0) + the K labels, all on the device; `modes`: the K blend-mode bytes
     (BLEND_MODES) in HOST memory, None = all 'basic'; `desc_host`: the descriptors once more as a host int32 array (K, 5) when the
     packer had them there (only a 'possion' paste needs them: its workspace is sized from the paste's rectangle), else None."""
@@ -50,48 +54,50 @@ class PackedPastes:
     def __len__(self):
         return self.K
 
+    def host_desc(self):
+        """The descriptors in host memory: `desc_host`, or else ONE device -> host copy of `desc`."""
+        return self.desc_host if self.desc_host is not None else self.desc.cpu().numpy()
+
+
+def _layout(pastes):
+    """list of (rgba (h, w, 4), x0, y0, label) -> ((K, 5) int32 numpy descriptors (byte offset, h, w, x0, y0), bytes of the flat buffer,
+    labels int64 numpy (K)).  A patch takes h * w * 4 bytes, so every patch starts on a 4-byte boundary without padding."""
+    desc, off = [], 0
+    for rgba, x0, y0, _ in pastes:
+        h, w = int(rgba.shape[0]), int(rgba.shape[1])
+        desc.append([off, h, w, int(x0), int(y0)])
+        off += h * w * 4
+    labels = np.array([int(np.asarray(p[3]).reshape(-1)[0]) for p in pastes], dtype=np.int64)
+    return np.asarray(desc, dtype=np.int32).reshape(-1, 5), off, labels
+
 
 def pack_pastes_host(pastes):
     """list of (rgba uint8 (h, w, 4) numpy, x0, y0, label) -> (flat uint8, desc int32 (K, 5), labels int64 (K)) as CPU tensors:
     what a LOADER WORKER hands the training process for one image (no device, no libdgx).  K = 0 gives a 4-byte flat buffer."""
-    desc, off = [], 0
-    for rgba, x0, y0, _ in pastes:
-        h, w = int(rgba.shape[0]), int(rgba.shape[1])
-        n = h * w * 4
-        desc.append([off, h, w, int(x0), int(y0)])
-        off += n + ((-n) % 4)
-    host = np.zeros(max(off, 4), dtype=np.uint8)
-    for (rgba, _, _, _), d in zip(pastes, desc):
+    desc, nbytes, labels = _layout(pastes)
+    host = np.zeros(max(nbytes, 4), dtype=np.uint8)
+    for (rgba, _, _, _), d in zip(pastes, desc.tolist()):
         n = d[1] * d[2] * 4
         a = rgba.detach().cpu().numpy() if isinstance(rgba, torch.Tensor) else np.asarray(rgba)
         host[d[0]:d[0] + n] = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
-    labels = np.array([int(np.asarray(p[3]).reshape(-1)[0]) for p in pastes], dtype=np.int64)
-    return torch.from_numpy(host), torch.from_numpy(np.asarray(desc, dtype=np.int32).reshape(-1, 5)), torch.from_numpy(labels)
+    return torch.from_numpy(host), torch.from_numpy(desc), torch.from_numpy(labels)
 
 
 def pack_pastes(pastes, device, modes=None, allow_poisson=False):
-    """allow_poisson: `modes` may name 'possion' (checked here, so that a wrong name fails where it is given).  modes: K blend modes (names or BLEND_MODES codes), None = all 'basic'.  list of (rgba uint8 (h, w, 4) numpy | tensor, x0, y0, label) -> PackedPastes.  Host arrays (the loader's case: patches come
-    out of the instance pool in host memory) are laid out in one host buffer and go up in ONE copy; patches that already live on
-    the device are gathered with one concatenation.  Round 2 concatenated 2 K device chunks per image inside every step, which
-    torch executes as one hipMemcpyAsync per chunk: 38 blit launches of ~10 us per image (0.8 ms per step on the loader stream)."""
+    """list of (rgba uint8 (h, w, 4) numpy | tensor, x0, y0, label) -> PackedPastes.  modes: K blend modes (names or BLEND_MODES
+    codes), None = all 'basic'; allow_poisson: `modes` may name 'possion' (checked here, so that a wrong name fails where it is
+    given).  Host arrays (the loader's case: patches come out of the instance pool in host memory) are laid out in one host buffer
+    and go up in ONE copy; patches that already live on the device are gathered with one concatenation.  Round 2 concatenated 2 K
+    device chunks per image inside every step, which torch executes as one hipMemcpyAsync per chunk: 38 blit launches of ~10 us
+    per image (0.8 ms per step on the loader stream)."""
     K = len(pastes)
     if modes is not None:
         host_modes(modes, K, allow_poisson)
     on_dev = [isinstance(r, torch.Tensor) and r.is_cuda for r, _, _, _ in pastes]
     if K and all(on_dev):
-        desc, off, chunks = [], 0, []
-        for rgba, x0, y0, _ in pastes:
-            h, w = int(rgba.shape[0]), int(rgba.shape[1])
-            n = h * w * 4
-            desc.append([off, h, w, int(x0), int(y0)])
-            off += n + ((-n) % 4)
-            chunks.append(rgba.reshape(-1))
-            if (-n) % 4:
-                chunks.append(torch.zeros((-n) % 4, dtype=torch.uint8, device=device))
-        flat = torch.cat(chunks)
-        desc_t = upload_i32(desc, device).view(-1, 5)
-        labels = upload_i32([int(np.asarray(p[3]).reshape(-1)[0]) for p in pastes], device).long()
-        return PackedPastes(flat, desc_t, labels, K, modes, np.asarray(desc, dtype=np.int32).reshape(-1, 5))
+        desc, _, labels = _layout(pastes)
+        flat = torch.cat([rgba.reshape(-1) for rgba, _, _, _ in pastes])
+        return PackedPastes(flat, upload_i32(desc, device).view(-1, 5), upload_i32(labels, device).long(), K, modes, desc)
     flat, desc, labels = pack_pastes_host(pastes)
     desc_host = desc.numpy().copy()
     if torch.device(device).type != "cuda":
@@ -146,7 +152,6 @@ def copy_paste(image, masks, boxes, labels, pastes, lazy_masks=False, modes=None
         return out
     pk = pastes if isinstance(pastes, PackedPastes) else pack_pastes(pastes, dev)
     hm = host_modes(modes if modes is not None else pk.modes, K, allow_poisson)
-    flat, desc_t = pk.flat, pk.desc
     image = image.contiguous().clone()
     masks = masks.contiguous()
     boxes0 = boxes.float().contiguous()
@@ -155,35 +160,44 @@ def copy_paste(image, masks, boxes, labels, pastes, lazy_masks=False, modes=None
     out_boxes = torch.empty(nobj, 4, dtype=torch.float32, device=dev)
     out_valid = torch.empty(nobj, dtype=torch.uint8, device=dev)
     stats = torch.empty(nobj * (K + 1) * 5 + 3 + H * W, dtype=torch.int32, device=dev)
+    args = (L.ptr(image), L.ptr(masks) if n0 else None, L.ptr(boxes0) if n0 else None, n0, H, W, L.ptr(pk.flat), L.ptr(pk.desc), K,
+            L.ptr(out_masks), L.ptr(out_boxes), L.ptr(out_valid), L.ptr(stats))
     report = None
-    if hm is not None and (hm == POISSON).any():
-        dh = pk.desc_host if getattr(pk, "desc_host", None) is not None else pk.desc.cpu().numpy()
-        nmax = max(poisson_unknowns(dh[k], H, W) for k in np.flatnonzero(hm == POISSON))
-        nbytes = int(L.lib().dgx_poisson_work_bytes(H, W, nmax))
-        work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
-        L.check(L.lib().dgx_copy_paste_blend_ws(L.ptr(image), L.ptr(masks) if n0 else None, L.ptr(boxes0) if n0 else None, n0, H, W,
-                                                L.ptr(flat), L.ptr(desc_t), K, L.ptr(out_masks), L.ptr(out_boxes), L.ptr(out_valid),
-                                                L.ptr(stats), hm.ctypes.data, L.ptr(work), nbytes, L.stream()), "dgx_copy_paste_blend_ws")
-        report = work[:4 * 32].view(32, 4)[:K]
-    elif hm is None:
-        L.check(L.lib().dgx_copy_paste(L.ptr(image), L.ptr(masks) if n0 else None, L.ptr(boxes0) if n0 else None, n0, H, W,
-                                       L.ptr(flat), L.ptr(desc_t), K, L.ptr(out_masks), L.ptr(out_boxes), L.ptr(out_valid),
-                                       L.ptr(stats), L.stream()), "dgx_copy_paste")
+    if hm is None:
+        entry = "dgx_copy_paste"
+    elif not (hm == POISSON).any():
+        entry, args = "dgx_copy_paste_blend", args + (hm.ctypes.data,)
     else:
-        L.check(L.lib().dgx_copy_paste_blend(L.ptr(image), L.ptr(masks) if n0 else None, L.ptr(boxes0) if n0 else None, n0, H, W,
-                                             L.ptr(flat), L.ptr(desc_t), K, L.ptr(out_masks), L.ptr(out_boxes), L.ptr(out_valid),
-                                             L.ptr(stats), hm.ctypes.data, L.stream()), "dgx_copy_paste_blend")
+        dh = pk.host_desc()
+        work, nbytes = _poisson_work(H, W, max(poisson_unknowns(dh[k], H, W) for k in np.flatnonzero(hm == POISSON)), dev)
+        entry, args = "dgx_copy_paste_blend_ws", args + (hm.ctypes.data, L.ptr(work), nbytes)
+        report = work[:POISSON_REPORT_RECORDS * POISSON_REPORT_FIELDS].view(POISSON_REPORT_RECORDS, POISSON_REPORT_FIELDS)[:K]
+    L.check(getattr(L.lib(), entry)(*args, L.stream()), entry)
     keep = out_valid.nonzero().squeeze(1)          # ONE compaction (and one device->host count) for the four per-object tensors
     all_labels = torch.cat([labels.to(torch.int64), pk.labels])
     source = torch.cat([torch.zeros(n0, dtype=torch.int64, device=dev), torch.ones(K, dtype=torch.int64, device=dev)])
-    out = dict(image=image, boxes=out_boxes.index_select(0, keep), labels=all_labels.index_select(0, keep), source=source.index_select(0, keep))
+    out = _compacted(image, out_masks, keep, lazy_masks, boxes=out_boxes, labels=all_labels, source=source)
+    if report is not None:
+        out["poisson_report"] = report
+    return out
+
+
+def _compacted(image, out_masks, keep, lazy_masks, **per_object):
+    """The result dict of copy_paste / self_copy_paste: `image`, the per-object tensors (boxes, labels, ...) gathered by `keep` in
+    the order given, then `masks` -- gathered too, or with lazy_masks all rows plus `keep`.  `keep` comes in computed: both callers
+    take it (the one device -> host count) before they build their per-object tensors."""
+    out = dict(image=image, **{name: t.index_select(0, keep) for name, t in per_object.items()})
     if lazy_masks:
         out["masks"], out["keep"] = out_masks, keep
     else:
         out["masks"] = out_masks.index_select(0, keep)
-    if report is not None:
-        out["poisson_report"] = report
     return out
+
+
+def _poisson_work(H, W, nmax, dev):
+    """The 'possion' solver's workspace for up to nmax unknowns in an (H, W) image -> (fp64 tensor, the report at its head; its bytes)."""
+    nbytes = int(L.lib().dgx_poisson_work_bytes(H, W, nmax))
+    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev), nbytes
 
 
 def poisson_blend(image, rgba, x0, y0, max_iter=-1):
@@ -193,12 +207,11 @@ def poisson_blend(image, rgba, x0, y0, max_iter=-1):
     H, W = int(image.shape[1]), int(image.shape[2])
     pk = pack_pastes([(rgba, x0, y0, 0)], dev)
     d = np.ascontiguousarray(pk.desc_host[0], dtype=np.int32)
-    nbytes = int(L.lib().dgx_poisson_work_bytes(H, W, poisson_unknowns(d, H, W)))
-    work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    work, nbytes = _poisson_work(H, W, poisson_unknowns(d, H, W), dev)
     image = image.contiguous().clone()
     L.check(L.lib().dgx_poisson_blend(L.ptr(image), L.ptr(pk.flat), d.ctypes.data, H, W, L.ptr(work), nbytes, int(max_iter),
                                       L.stream()), "dgx_poisson_blend")
-    return image, work[:4]
+    return image, work[:POISSON_REPORT_FIELDS]
 
 
 SELF_COPY_MAX = 99      # dgx_self_copy_paste: m <= 99 (the reference draws m < min(ns + 1, 100))
@@ -257,9 +270,4 @@ def self_copy_paste(image, masks, boxes, labels, src_image, src_masks, src_boxes
     keep = torch.cat([out_valid, torch.ones(m, dtype=torch.uint8, device=dev)]).nonzero().squeeze(1)      # ONE compaction
     all_boxes = torch.cat([out_boxes, sel_boxes])
     all_labels = torch.cat([labels.to(torch.int64), src_labels.to(torch.int64).index_select(0, sel_t.long())])
-    out = dict(image=out_image, boxes=all_boxes.index_select(0, keep), labels=all_labels.index_select(0, keep))
-    if lazy_masks:
-        out["masks"], out["keep"] = out_masks, keep
-    else:
-        out["masks"] = out_masks.index_select(0, keep)
-    return out
+    return _compacted(out_image, out_masks, keep, lazy_masks, boxes=all_boxes, labels=all_labels)
