@@ -161,6 +161,10 @@ def get_cfg():
     #   conjugate-gradient solve on the device and rewrites the image frame, as the reference's poisson_edit does
     #   (divergen_amd/csrc/poisson_blend.hip); without the key 'possion' is refused at start-up.
     cfg.INPUT.CP_POISSON = False
+    #   INPUT.SCP_MULTI_SRC: admits INPUT.SCP_NUM_SRC 2 .. 4 to the self-copy methods of INPUT.USE_COPY_METHOD: the sources are merged
+    #   on the device first (divergen_amd/csrc/self_copy_merge.hip), which costs one more read-back of validity bytes and boxes per
+    #   sample; without the key SCP_NUM_SRC != 1 is refused at start-up.
+    cfg.INPUT.SCP_MULTI_SRC = False
     #   SOLVER.ALLREDUCE_DTYPE: "fp32" (the reference's DDP: gradients all-reduced as they are) or "bf16" (gradient buckets go over
     #   xGMI as bf16, half the bytes per step; engine/ddp.py ArenaReducer(wire_dtype=...)).
     cfg.SOLVER.ALLREDUCE_DTYPE = "fp32"

@@ -12,50 +12,11 @@
 //                 reduced over the wave, then LDS, then one global atomic set per workgroup and touched object
 //   k3 resolve  : one lane per destination object: mask-derived box, the occlusion filter
 // Rows / columns beyond (h1, w1) of the destination or (hs, ws) of the source read as 0 without touching memory.
-#include "dgx_common.h"
-
-#define SC_MAX_M 99
-constexpr int SCX = 16;                            // pixels per lane
-constexpr int SC_MAX_OPG = 64;                     // destination objects per workgroup group (LDS statistics)
-
-// 16 bytes of row y, columns x .. x + 15 of an (h, w) plane; zeros outside.  vec: w % 16 == 0 and a 16-byte aligned base, so a
-// chunk that starts inside the row lies inside it.
-__device__ __forceinline__ void sc_load16(const uint8_t* __restrict__ plane, int y, int x, int h, int w, bool vec, uint32_t (&v)[4]) {
-    v[0] = v[1] = v[2] = v[3] = 0u;
-    if (y >= h || x >= w) return;
-    const uint8_t* p = plane + (int64_t)y * w + x;
-    if (vec) {
-        const uint4 t = *reinterpret_cast<const uint4*>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int q = 0; q < SCX; ++q)
-            if (x + q < w) v[q >> 2] |= (uint32_t)p[q] << (8 * (q & 3));
-    }
-}
-
-__device__ __forceinline__ void sc_store16(uint8_t* __restrict__ plane, int y, int x, int W, bool vec, const uint32_t (&v)[4]) {
-    uint8_t* p = plane + (int64_t)y * W + x;
-    if (vec) {
-        *reinterpret_cast<uint4*>(p) = make_uint4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-        for (int q = 0; q < SCX; ++q)
-            if (x + q < W) p[q] = (uint8_t)(v[q >> 2] >> (8 * (q & 3)));
-    }
-}
-
-// per byte: 0x01 where the byte is non-zero
-__device__ __forceinline__ uint32_t sc_nonzero(uint32_t w) {
-    return ((((w & 0x7f7f7f7fu) + 0x7f7f7f7fu) | w) >> 7) & 0x01010101u;
-}
+#include "self_copy_common.h"
 
 __global__ void sc_init_kernel(int32_t* __restrict__ stats, int n0, uint32_t* __restrict__ composed, int64_t nwords) {
     const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = i0; i < (int64_t)n0 * 5; i += step) {
-        const int f = (int)(i % 5);
-        stats[i] = f == 0 ? 0 : ((f == 1 || f == 3) ? 0x7fffffff : -1);
-    }
+    for (int64_t i = i0; i < (int64_t)n0 * 5; i += step) stats[i] = sc_stat_init((int)(i % 5));
     for (int64_t i = i0; i < nwords; i += step) composed[i] = 0u;
 }
 
@@ -98,10 +59,7 @@ __global__ __launch_bounds__(256) void sc_dest_kernel(const uint8_t* __restrict_
                                                       uint8_t* __restrict__ out_masks, int32_t* __restrict__ stats) {
     __shared__ int32_t s[SC_MAX_OPG * 5];
     const int oa = blockIdx.y * per_group, ob = min(n0, oa + per_group);
-    for (int i = threadIdx.x; i < (ob - oa) * 5; i += blockDim.x) {
-        const int f = i % 5;
-        s[i] = f == 0 ? 0 : ((f == 1 || f == 3) ? 0x7fffffff : -1);
-    }
+    for (int i = threadIdx.x; i < (ob - oa) * 5; i += blockDim.x) s[i] = sc_stat_init(i % 5);
     __syncthreads();
     const int64_t HW = (int64_t)H * W, dhw = (int64_t)h1 * w1, shw = (int64_t)hs * ws, nchunk = (int64_t)H * ncx;
     const int lane = threadIdx.x & 63;
@@ -127,46 +85,18 @@ __global__ __launch_bounds__(256) void sc_dest_kernel(const uint8_t* __restrict_
             }
         }
         for (int obj = oa; obj < ob; ++obj) {
-            int cnt = 0, x0 = 0x7fffffff, x1 = -1;
+            uint32_t v[4] = {0u, 0u, 0u, 0u};
             if (active) {
-                uint32_t v[4];
                 sc_load16(dst_masks + obj * dhw, y, x, h1, w1, fl.dst_vec, v);
-                uint32_t bits = 0;                 // bit q: pixel x + q survives
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    v[q] &= keep[q];
-                    const uint32_t nz = sc_nonzero(v[q]);
-                    bits |= ((nz & 1u) | ((nz >> 7) & 2u) | ((nz >> 14) & 4u) | ((nz >> 21) & 8u)) << (4 * q);
-                }
+                for (int q = 0; q < 4; ++q) v[q] &= keep[q];
                 sc_store16(out_masks + obj * HW, y, x, W, fl.out_vec, v);
-                if (bits) { cnt = __popc(bits); x0 = x + __ffs((int)bits) - 1; x1 = x + 31 - __clz((int)bits); }
             }
-            if (__any(cnt > 0)) {                  // wave-uniform
-                int y0 = cnt ? y : 0x7fffffff, y1 = cnt ? y : -1;
-#pragma unroll
-                for (int d = 32; d >= 1; d >>= 1) {
-                    cnt += __shfl_xor(cnt, d);
-                    x0 = min(x0, __shfl_xor(x0, d)); x1 = max(x1, __shfl_xor(x1, d));
-                    y0 = min(y0, __shfl_xor(y0, d)); y1 = max(y1, __shfl_xor(y1, d));
-                }
-                if (lane == 0) {
-                    int32_t* r = s + 5 * (obj - oa);
-                    atomicAdd(&r[0], cnt);
-                    atomicMin(&r[1], x0); atomicMax(&r[2], x1);
-                    atomicMin(&r[3], y0); atomicMax(&r[4], y1);
-                }
-            }
+            sc_fold_stats(v, y, x, lane, s + 5 * (obj - oa));
         }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < (ob - oa) * 5; i += blockDim.x) {
-        const int f = i % 5;
-        if (s[5 * (i / 5)] == 0) continue;
-        int32_t* g = stats + (int64_t)oa * 5 + i;
-        if (f == 0) atomicAdd(g, s[i]);
-        else if (f == 1 || f == 3) atomicMin(g, s[i]);
-        else atomicMax(g, s[i]);
-    }
+    sc_flush_stats(s, ob - oa, stats + (int64_t)oa * 5);
 }
 
 // get_bboxes of the updated mask (x_max + 1, y_max + 1; zeros when empty), then _copy_paste's filter: kept when every
@@ -175,22 +105,18 @@ __global__ void sc_resolve_kernel(const int32_t* __restrict__ stats, const float
                                   float* __restrict__ out_boxes, uint8_t* __restrict__ out_valid) {
     const int obj = blockIdx.x * blockDim.x + threadIdx.x;
     if (obj >= n0) return;
-    const int32_t* s = stats + 5 * obj;
-    float b[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (s[0] > 0) { b[0] = (float)s[1]; b[1] = (float)s[3]; b[2] = (float)(s[2] + 1); b[3] = (float)(s[4] + 1); }
-    bool box_ok = true;
-    for (int i = 0; i < 4; ++i) {
-        box_ok = box_ok && fabsf(b[i] - boxes0[4 * obj + i]) <= 10.0f;
-        out_boxes[4 * obj + i] = b[i];
-    }
-    out_valid[obj] = (m == 0 || box_ok || s[0] > 300) ? 1 : 0;
+    float b[4];
+    const bool ok = sc_resolve(stats + 5 * obj, boxes0 + 4 * obj, b);
+    for (int i = 0; i < 4; ++i) out_boxes[4 * obj + i] = b[i];
+    out_valid[obj] = (m == 0 || ok) ? 1 : 0;
 }
 
-extern "C" int dgx_self_copy_paste(const uint8_t* dst_image, const uint8_t* dst_masks, const float* dst_boxes0, int n0, int h1, int w1,
-                                   const uint8_t* src_image, const uint8_t* src_masks, int ns, int hs, int ws,
-                                   const int32_t* sel, int m, int H, int W, uint8_t* out_image, uint8_t* out_masks,
-                                   float* out_boxes, uint8_t* out_valid, int32_t* workspace, void* stream) {
-    if (n0 < 0 || ns < 0 || m < 0 || m > SC_MAX_M || h1 <= 0 || w1 <= 0 || H < h1 || W < w1 || (m > 0 && (ns <= 0 || hs <= 0 || ws <= 0)))
+// max_m: 99 for one source image; 99 per merged source when the planes come out of dgx_self_copy_merge
+static int sc_paste(const uint8_t* dst_image, const uint8_t* dst_masks, const float* dst_boxes0, int n0, int h1, int w1,
+                    const uint8_t* src_image, const uint8_t* src_masks, int ns, int hs, int ws, const int32_t* sel, int m, int max_m,
+                    int H, int W, uint8_t* out_image, uint8_t* out_masks, float* out_boxes, uint8_t* out_valid, int32_t* workspace,
+                    void* stream) {
+    if (n0 < 0 || ns < 0 || m < 0 || m > max_m || h1 <= 0 || w1 <= 0 || H < h1 || W < w1 || (m > 0 && (ns <= 0 || hs <= 0 || ws <= 0)))
         return DGX_ERR_BAD_ARG;
     if (!dst_image || !out_image || !workspace || ((uintptr_t)workspace & 15) || (n0 > 0 && (!dst_masks || !dst_boxes0 || !out_boxes || !out_valid)) ||
         (m > 0 && (!src_image || !src_masks || !sel)) || (n0 + m > 0 && !out_masks))
@@ -213,7 +139,9 @@ extern "C" int dgx_self_copy_paste(const uint8_t* dst_image, const uint8_t* dst_
     const int gx = (int)((nchunk + 255) / 256 < 2048 ? (nchunk + 255) / 256 : 2048);
     const int want = gx >= 1024 ? 1 : (1024 + gx - 1) / gx;
     if (m > 0) {
-        const int groups = want < m ? want : m, per = (m + groups - 1) / groups;
+        const int groups = want < m ? want : m;
+        int per = (m + groups - 1) / groups;
+        if (per > SC_MAX_M) per = SC_MAX_M;          // s_sel holds one group's indices (only a merged source has m > 99)
         hipLaunchKernelGGL(sc_source_kernel, dim3(gx, (m + per - 1) / per), dim3(256), 0, st, src_masks, ns, hs, ws, sel, m, per, n0,
                            H, W, ncx, fl, out_masks, composed);
     }
@@ -230,4 +158,20 @@ extern "C" int dgx_self_copy_paste(const uint8_t* dst_image, const uint8_t* dst_
         hipLaunchKernelGGL(sc_resolve_kernel, dim3((n0 + 63) / 64), dim3(64), 0, st, workspace, dst_boxes0, n0, m, out_boxes, out_valid);
     DGX_LAUNCH_CHECK();
     return DGX_OK;
+}
+
+extern "C" int dgx_self_copy_paste(const uint8_t* dst_image, const uint8_t* dst_masks, const float* dst_boxes0, int n0, int h1, int w1,
+                                   const uint8_t* src_image, const uint8_t* src_masks, int ns, int hs, int ws,
+                                   const int32_t* sel, int m, int H, int W, uint8_t* out_image, uint8_t* out_masks,
+                                   float* out_boxes, uint8_t* out_valid, int32_t* workspace, void* stream) {
+    return sc_paste(dst_image, dst_masks, dst_boxes0, n0, h1, w1, src_image, src_masks, ns, hs, ws, sel, m, SC_MAX_M, H, W, out_image,
+                    out_masks, out_boxes, out_valid, workspace, stream);
+}
+
+extern "C" int dgx_self_copy_paste_merged(const uint8_t* dst_image, const uint8_t* dst_masks, const float* dst_boxes0, int n0, int h1, int w1,
+                                          const uint8_t* src_image, const uint8_t* src_masks, int ns, int hs, int ws,
+                                          const int32_t* sel, int m, int H, int W, uint8_t* out_image, uint8_t* out_masks,
+                                          float* out_boxes, uint8_t* out_valid, int32_t* workspace, void* stream) {
+    return sc_paste(dst_image, dst_masks, dst_boxes0, n0, h1, w1, src_image, src_masks, ns, hs, ws, sel, m, SC_MAX_M * SCM_MAX_SRC, H, W,
+                    out_image, out_masks, out_boxes, out_valid, workspace, stream);
 }

@@ -458,7 +458,8 @@ class CopyPasteMapper:
     pool -> InstPool.get_mix_result (divergen_amd/data/copypaste.py, pixels on the GPU compositor); the self-copy branch has
     no mix results in that configuration, so SimpleCopyPaste returns its input (custom_copypaste.py:254-259).
     USE_COPY_METHOD 'self_copy' / 'both' / 'p:<f>' (mapper.py:884-936): Simple Copy-Paste from a second training image
-    (custom_copypaste.py:242-341), worker half in _call_self_copy, pixels in dgx_self_copy_paste (_finish_self_copy)."""
+    (custom_copypaste.py:242-341), worker half in _call_self_copy, pixels in dgx_self_copy_paste (_finish_self_copy); with
+    INPUT.SCP_MULTI_SRC from INPUT.SCP_NUM_SRC <= 4 images, merged by dgx_self_copy_merge first."""
 
     def __init__(self, mapper, cfg):
         self.mapper = mapper
@@ -505,11 +506,17 @@ class CopyPasteMapper:
 
     @staticmethod
     def _check_self_copy(cfg):
-        """The self-copy branch is built for SCP_TYPE '', one source image, selected objects, 'basic' blend (the reference's own
-        choice, mapper.py:770); every other switch of that branch is refused by name."""
+        """The self-copy branch is built for SCP_TYPE '', one source image (up to SELF_COPY_MAX_SRC with this build's key
+        INPUT.SCP_MULTI_SRC), selected objects, 'basic' blend (the reference's own choice, mapper.py:770); every other switch of that
+        branch is refused by name."""
+        from ..layers.copy_paste import SELF_COPY_MAX_SRC
         inp = cfg.INPUT
+        if bool(inp.get("SCP_MULTI_SRC", False)) and not 1 <= inp.SCP_NUM_SRC <= SELF_COPY_MAX_SRC:
+            raise NotImplementedError("INPUT.SCP_NUM_SRC {!r} with INPUT.USE_COPY_METHOD '{}': INPUT.SCP_MULTI_SRC merges 1 to {} source "
+                                      "images (dgx_self_copy_merge)".format(inp.SCP_NUM_SRC, inp.USE_COPY_METHOD, SELF_COPY_MAX_SRC))
         refused = [("SCP_TYPE", inp.SCP_TYPE != "", "only '' (a random training image as the source)"),
-                   ("SCP_NUM_SRC", inp.SCP_NUM_SRC != 1, "only 1 (several sources are merged on a temporary canvas first)"),
+                   ("SCP_NUM_SRC", inp.SCP_NUM_SRC != 1 and not bool(inp.get("SCP_MULTI_SRC", False)),
+                    "only 1 (several sources are merged on a temporary canvas first)"),
                    ("SCP_SRC_OBJ_SELECT", not inp.SCP_SRC_OBJ_SELECT, "only True"),
                    ("BLANK_RATIO", inp.BLANK_RATIO > 0, "the source is not resized (needs cv2.resize)"),
                    ("ROTATE_SRC", bool(inp.ROTATE_SRC), "the source is not rotated"),
@@ -563,12 +570,11 @@ class CopyPasteMapper:
         result = self.mapper(dataset_dict)
         if "instances" not in result or not result["instances"].has("gt_masks"):        # mapper.py:862-864
             return result
-        idx = None
+        idxs = []
         if self.use_scp and self.dataset is not None:
-            for _ in range(self.num_src):
-                idx = np.random.randint(0, len(self.dataset))
-        if self.self_prob is not None and idx is not None:
-            return self._call_self_copy(result, idx)
+            idxs = [np.random.randint(0, len(self.dataset)) for _ in range(self.num_src)]
+        if self.self_prob is not None and idxs:
+            return self._call_self_copy(result, idxs)
         if self.inst_pool is None:
             return result
         result = self.inst_pool.prepare(result)
@@ -578,58 +584,76 @@ class CopyPasteMapper:
             result["test_image_class"], result["test_file_name"] = cls, test.get("file_name")
         return pack_sample(result) if self.pack else result
 
-    def _call_self_copy(self, result, idx):
+    def _call_self_copy(self, result, idxs):
         """The self-copy methods (mapper.py:884-936 + CopyPaste._select_object, custom_copypaste.py:393-411), worker half, in the
-        reference's np.random order: [rand() for 'p:<f>'] -> the source image through the same mapper (its own resize-crop and flip
-        draws) -> the instance pool's draws when the sample takes the pool branch -> m = randint(0, min(ns + 1, 100)),
-        sel = choice(ns, m, replace=False).  Adds `scp_src`: the source image, the m selected masks / boxes / labels in paste order
-        and the canvas size -- what dgx_self_copy_paste needs; the training process runs it (finish)."""
+        reference's np.random order: [rand() for 'p:<f>'] -> the source images through the same mapper, in index order (each its own
+        resize-crop and flip draws) -> the instance pool's draws when the sample takes the pool branch -> per source, in order,
+        m = randint(0, min(ns + 1, 100)), sel = choice(ns, m, replace=False).  Adds `scp_src`: the source image, the m selected
+        masks / boxes / labels in paste order and the canvas size -- what dgx_self_copy_paste needs; the training process runs it
+        (finish).  With INPUT.SCP_NUM_SRC > 1 the sources that selected nothing are skipped as the reference skips them; one left is
+        the case above, byte for byte; two or more make `scp_src` a LIST of such groups (no canvas: it follows from the merge), each
+        cropped to the largest box extent of all of them, beyond which no stage's canvas reaches."""
         from ..layers.copy_paste import self_copy_canvas
         take_self, take_syn = True, self.method == "both"
         if self.method.startswith("p:"):
             take_self = np.random.rand() < self.self_prob
             take_syn = not take_self
-        src = self.mapper(self.dataset[idx]) if take_self else None
+        srcs = [self.mapper(self.dataset[i]) for i in idxs] if take_self else []
         if take_syn and self.inst_pool is not None:
             result = self.inst_pool.prepare(result)
         if take_self:
             result = dict(result)
-            si = src["instances"]
-            ns = len(si)
-            m = np.random.randint(0, min(ns + 1, 100))
-            sel = np.random.choice(ns, size=m, replace=False)
+            picked = []                                        # (source, selected indices) of the sources that selected something
+            for src in srcs:
+                ns = len(src["instances"])
+                m = np.random.randint(0, min(ns + 1, 100))
+                sel = np.random.choice(ns, size=m, replace=False)
+                if m:
+                    picked.append((src, torch.from_numpy(np.asarray(sel, dtype=np.int64))))
             h1, w1 = result["image"].shape[-2:]
-            if m:
-                sel_t = torch.from_numpy(np.asarray(sel, dtype=np.int64))
-                boxes = si.gt_boxes.tensor[sel_t]
-                H, W = self_copy_canvas((h1, w1), boxes)
+
+            def group(src, sel_t, H, W):
                 # only what the canvas can show travels: the source cropped to (H, W) (the kernel zero-pads a smaller one)
-                result["scp_src"] = {"image": src["image"][:, :H, :W].contiguous(),
-                                     "masks": si.gt_masks.tensor.view(torch.uint8)[sel_t][:, :H, :W].contiguous(),
-                                     "boxes": boxes.contiguous(), "labels": si.gt_classes[sel_t].contiguous(), "hw": (H, W)}
-                if self.inst_pool is not None:
-                    self.inst_pool.draw_modes(1)          # blend_image's `random.sample(['basic'], 1)` of this paste (custom_copypaste.py:467)
+                si = src["instances"]
+                return {"image": src["image"][:, :H, :W].contiguous(),
+                        "masks": si.gt_masks.tensor.view(torch.uint8)[sel_t][:, :H, :W].contiguous(),
+                        "boxes": si.gt_boxes.tensor[sel_t].contiguous(), "labels": si.gt_classes[sel_t].contiguous()}
+            if len(picked) == 1:
+                src, sel_t = picked[0]
+                H, W = self_copy_canvas((h1, w1), src["instances"].gt_boxes.tensor[sel_t])
+                result["scp_src"] = dict(group(src, sel_t, H, W), hw=(H, W))
+            elif picked:
+                H, W = self_copy_canvas((0, 0), torch.cat([src["instances"].gt_boxes.tensor[sel_t] for src, sel_t in picked]))
+                result["scp_src"] = [group(src, sel_t, H, W) for src, sel_t in picked]
             else:                                          # nothing pasted; the Instances is still rebuilt (custom_copypaste.py:311-318)
                 result["scp_src"] = {"image": torch.zeros(3, 0, 0, dtype=torch.uint8), "masks": torch.zeros(0, 0, 0, dtype=torch.uint8),
                                      "boxes": torch.zeros(0, 4), "labels": torch.zeros(0, dtype=torch.int64), "hw": (int(h1), int(w1))}
-            result["scp_file_name"] = src.get("file_name")
+            if self.inst_pool is not None and picked:
+                # blend_image's `random.sample(['basic'], 1)` (custom_copypaste.py:467), once per _copy_paste that happens: the
+                # len(picked) - 1 temporary stages and the final paste
+                self.inst_pool.draw_modes(len(picked))
+            result["scp_file_name"] = srcs[0].get("file_name") if len(srcs) == 1 else [src.get("file_name") for src in srcs]
         return pack_sample(result) if self.pack else result
 
     @staticmethod
     def _finish_self_copy(out, scp, dev):
-        """Training-process half of the self copy: ONE dgx_self_copy_paste call on the current stream, then the Instances rebuilt with
+        """Training-process half of the self copy: ONE dgx_self_copy_paste call on the current stream (a list of source groups:
+        layers.self_copy_paste_multi -- dgx_self_copy_merge, one read-back, dgx_self_copy_paste_merged), then the Instances rebuilt with
         gt_boxes / gt_classes / gt_masks only (custom_copypaste.py:311-318: instance_source and every other field are gone, also
         when nothing was pasted)."""
-        from ..layers.copy_paste import self_copy_paste
+        from ..layers.copy_paste import self_copy_paste, self_copy_paste_multi
         from .copypaste import result_instances
         if dev.type != "cuda":
             raise RuntimeError("INPUT.USE_COPY_METHOD with a self copy needs the GPU compositor (dgx_self_copy_paste); device is %s" % dev)
         inst = out["instances"]
         up = lambda t: t.to(dev, non_blocking=True)     # noqa: E731
-        m = int(scp["labels"].shape[0])
-        r = self_copy_paste(out["image"], inst.gt_masks.tensor.view(torch.uint8), inst.gt_boxes.tensor, inst.gt_classes,
-                            up(scp["image"]), up(scp["masks"]), up(scp["boxes"]), up(scp["labels"]), np.arange(m),
-                            canvas_hw=scp["hw"], lazy_masks=True)
+        dst = (out["image"], inst.gt_masks.tensor.view(torch.uint8), inst.gt_boxes.tensor, inst.gt_classes)
+        if isinstance(scp, list):      # several sources (INPUT.SCP_MULTI_SRC): dgx_self_copy_merge, one read-back, then the paste
+            r = self_copy_paste_multi(*dst, [tuple(up(g[k]) for k in ("image", "masks", "boxes", "labels")) for g in scp], lazy_masks=True)
+        else:
+            m = int(scp["labels"].shape[0])
+            r = self_copy_paste(*dst, up(scp["image"]), up(scp["masks"]), up(scp["boxes"]), up(scp["labels"]), np.arange(m),
+                                canvas_hw=scp["hw"], lazy_masks=True)
         out["instances"] = result_instances(r, with_source=False)
         out["image"], (out["height"], out["width"]) = r["image"], out["instances"].image_size
         return out
@@ -678,15 +702,26 @@ _BLOB_SCP_FIELDS = (("scp_image", lambda d: d["scp_src"]["image"]), ("scp_masks"
                     ("scp_boxes", lambda d: d["scp_src"]["boxes"]), ("scp_labels", lambda d: d["scp_src"]["labels"]))
 
 
+def _blob_scp_group_fields(i):
+    """The four sections of source group i of a sample whose scp_src is a LIST (INPUT.SCP_NUM_SRC > 1, two or more sources selected
+    something): scp<i>_image, scp<i>_masks, scp<i>_boxes, scp<i>_labels."""
+    return tuple(("scp%d_%s" % (i, k), lambda d, i=i, k=k: d["scp_src"][i][k]) for k in ("image", "masks", "boxes", "labels"))
+
+
 def pack_sample(d):
     """Worker side: the sample's tensors -> d['blob'] (uint8) + d['blob_layout'] [(name, dtype, shape, byte offset)]; the tensor
     entries themselves are dropped.  Samples without paste_pack / instances pass through unchanged.  Sections: the four of the
-    sample, the three of paste_pack when it has one, the four of the self-copy source (scp_src) when it has one; a sample
-    without scp_src packs exactly as it always did."""
+    sample, the three of paste_pack when it has one, the four of the self-copy source (scp_src) when it has one -- four per group
+    when scp_src is a list of source groups, counted by blob_scp_n; a sample without scp_src, and one with a single source, pack
+    exactly as they always did."""
     if ("paste_pack" not in d and "scp_src" not in d) or "instances" not in d or not d["instances"].has("gt_masks"):
         return d
     fields = _BLOB_FIELDS if "paste_pack" in d else _BLOB_FIELDS[:4]
-    if "scp_src" in d:
+    multi = isinstance(d.get("scp_src"), list)
+    if multi:
+        for i in range(len(d["scp_src"])):
+            fields = fields + _blob_scp_group_fields(i)
+    elif "scp_src" in d:
         fields = fields + _BLOB_SCP_FIELDS
     parts, layout, off = [], [], 0
     for name, get in fields:
@@ -701,7 +736,9 @@ def pack_sample(d):
     out = {k: v for k, v in d.items() if k not in ("image", "instances", "paste_pack", "scp_src")}
     out["blob"], out["blob_layout"] = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.uint8), layout
     out["blob_hw"] = tuple(d["image"].shape[-2:])
-    if "scp_src" in d:
+    if multi:
+        out["blob_scp_n"] = len(d["scp_src"])
+    elif "scp_src" in d:
         out["blob_scp_hw"] = tuple(int(v) for v in d["scp_src"]["hw"])
     if "paste_pack" in d:
         out["blob_K"] = int(d["paste_pack"]["K"])
@@ -754,6 +791,8 @@ def unpack_sample(d, device, ring=None):
     if "scp_image" in f:
         out["scp_src"] = {"image": f["scp_image"], "masks": f["scp_masks"], "boxes": f["scp_boxes"], "labels": f["scp_labels"],
                           "hw": tuple(d["blob_scp_hw"])}
+    if d.get("blob_scp_n"):
+        out["scp_src"] = [{k: f["scp%d_%s" % (i, k)] for k in ("image", "masks", "boxes", "labels")} for i in range(d["blob_scp_n"])]
     return out
 
 
@@ -953,7 +992,8 @@ def build_detection_train_loader(cfg, per_gpu, device, seed):
         # with a self-copy method the sample also carries the source image (3 planes) and up to 99 selected source masks, each at most
         # TRAIN_SIZE^2: room for ~45 more planes (the mean of the draw over a 90-object image); beyond that, the ordinary way again
         size = int(cfg.INPUT.TRAIN_SIZE)
-        planes = 48 if mapper.self_prob is None else 96
+        # (INPUT.SCP_NUM_SRC sources: that many times the source's share)
+        planes = 48 if mapper.self_prob is None else 48 + 48 * int(mapper.num_src)
         try:
             ring = SlotRing(nw, (int(cfg.DATALOADER.PREFETCH_FACTOR) + 2) * per_gpu, size * size * planes + (8 << 20))
         except Exception as e:

@@ -1,6 +1,6 @@
 """Instance copy-paste compositor on the GPU: the 'basic', 'alpha', 'gaussian' and (opt-in) 'possion' blends of all K pastes of an
-image in one libdgx call (copy_paste), one 'possion' paste alone (poisson_blend), and the self copy between two real images
-(self_copy_paste).  Reference: DG/divergen/data/custom_build_copypaste_mapper.py:488-566, :79-92; custom_cp_method.py:5-18."""
+image in one libdgx call (copy_paste), one 'possion' paste alone (poisson_blend), the self copy between two real images
+(self_copy_paste) and from several source images (self_copy_merge, self_copy_paste_multi).  Reference: DG/divergen/data/custom_build_copypaste_mapper.py:488-566, :79-92; custom_cp_method.py:5-18."""
 import numpy as np
 import torch
 
@@ -215,6 +215,7 @@ def poisson_blend(image, rgba, x0, y0, max_iter=-1):
 
 
 SELF_COPY_MAX = 99      # dgx_self_copy_paste: m <= 99 (the reference draws m < min(ns + 1, 100))
+SELF_COPY_MAX_SRC = 4   # dgx_self_copy_merge: S <= 4 source images (DGX_SELF_COPY_MAX_SRC): the bound of INPUT.SCP_NUM_SRC
 
 
 def self_copy_canvas(dst_hw, sel_boxes):
@@ -225,7 +226,8 @@ def self_copy_canvas(dst_hw, sel_boxes):
     return max(int(dst_hw[0]), math.ceil(b[..., 3].max())), max(int(dst_hw[1]), math.ceil(b[..., 2].max()))
 
 
-def self_copy_paste(image, masks, boxes, labels, src_image, src_masks, src_boxes, src_labels, sel, canvas_hw=None, lazy_masks=False):
+def self_copy_paste(image, masks, boxes, labels, src_image, src_masks, src_boxes, src_labels, sel, canvas_hw=None, lazy_masks=False,
+                    merged=False):
     """Simple Copy-Paste between two real images, one paste step (CopyPaste._scp_src_to_dst + _copy_paste,
     DG/divergen/data/transforms/custom_copypaste.py:343-389, :428-506, 'basic' blend) in ONE dgx_self_copy_paste call.
     image uint8 (3,h1,w1), masks uint8 (n0,h1,w1), boxes f32 (n0,4), labels i64 (n0): the destination, GPU tensors.
@@ -235,13 +237,15 @@ def self_copy_paste(image, masks, boxes, labels, src_image, src_masks, src_boxes
     Returns dict(image, masks, boxes, labels) like copy_paste (no `source`): the surviving destination objects with the boxes of their
     updated masks, then the m selected source objects with their own boxes -- ONE compaction by out_valid.  m == 0: nothing is
     pasted, the inputs come back as they are (the reference keeps the destination's boxes then).
-    lazy_masks: `masks` holds ALL n0 + m rows and `keep` (i64) the rows of the surviving objects, for BitMasks(masks, index=keep)."""
+    lazy_masks: `masks` holds ALL n0 + m rows and `keep` (i64) the rows of the surviving objects, for BitMasks(masks, index=keep).
+    merged: the source is the accumulator of self_copy_merge (dgx_self_copy_paste_merged: up to 99 objects per merged source)."""
     dev = image.device
     sel = np.asarray(sel, dtype=np.int64).reshape(-1)
     m, n0, ns = int(sel.shape[0]), int(masks.shape[0]), int(src_masks.shape[0])
     h1, w1 = int(image.shape[1]), int(image.shape[2])
-    if m > SELF_COPY_MAX:
-        raise ValueError("self_copy_paste: %d source objects selected, at most %d" % (m, SELF_COPY_MAX))
+    entry, most = ("dgx_self_copy_paste_merged", SELF_COPY_MAX * SELF_COPY_MAX_SRC) if merged else ("dgx_self_copy_paste", SELF_COPY_MAX)
+    if m > most:
+        raise ValueError("self_copy_paste: %d source objects selected, at most %d" % (m, most))
     if m and (int(sel.min()) < 0 or int(sel.max()) >= ns):
         raise ValueError("self_copy_paste: selected source index outside [0, %d): %s" % (ns, sel.tolist()))
     if m == 0:
@@ -263,11 +267,70 @@ def self_copy_paste(image, masks, boxes, labels, src_image, src_masks, src_boxes
     out_boxes = torch.empty(n0, 4, dtype=torch.float32, device=dev)
     out_valid = torch.empty(n0, dtype=torch.uint8, device=dev)
     work = torch.empty(((n0 * 5 + 3) & ~3) + H * ((W + 15) // 16) * 4, dtype=torch.int32, device=dev)
-    L.check(L.lib().dgx_self_copy_paste(L.ptr(image), L.ptr(masks) if n0 else None, L.ptr(boxes0) if n0 else None, n0, h1, w1,
-                                        L.ptr(src_image), L.ptr(src_masks), ns, hs, ws, L.ptr(sel_t), m, H, W,
-                                        L.ptr(out_image), L.ptr(out_masks), L.ptr(out_boxes) if n0 else None,
-                                        L.ptr(out_valid) if n0 else None, L.ptr(work), L.stream()), "dgx_self_copy_paste")
+    L.check(getattr(L.lib(), entry)(L.ptr(image), L.ptr(masks) if n0 else None, L.ptr(boxes0) if n0 else None, n0, h1, w1,
+                                    L.ptr(src_image), L.ptr(src_masks), ns, hs, ws, L.ptr(sel_t), m, H, W,
+                                    L.ptr(out_image), L.ptr(out_masks), L.ptr(out_boxes) if n0 else None,
+                                    L.ptr(out_valid) if n0 else None, L.ptr(work), L.stream()), entry)
     keep = torch.cat([out_valid, torch.ones(m, dtype=torch.uint8, device=dev)]).nonzero().squeeze(1)      # ONE compaction
     all_boxes = torch.cat([out_boxes, sel_boxes])
     all_labels = torch.cat([labels.to(torch.int64), src_labels.to(torch.int64).index_select(0, sel_t.long())])
     return _compacted(out_image, out_masks, keep, lazy_masks, boxes=all_boxes, labels=all_labels)
+
+
+def self_copy_merge(sources):
+    """The temporary stages of Simple Copy-Paste from several source images (CopyPaste.__call__,
+    DG/divergen/data/transforms/custom_copypaste.py:274-297: the first source is the accumulator, every further one is pasted onto it
+    on a canvas taken from the boxes alone) in ONE dgx_self_copy_merge call: all S - 1 stages on the current stream, no host round trip.
+    sources: 2 <= S <= 4 tuples (image uint8 (3,h_i,w_i), masks uint8 (m_i,h_i,w_i), boxes f32 (m_i,4), labels i64 (m_i)) of GPU
+    tensors: the SELECTED objects of each source image in paste order, 1 <= m_i <= 99 (a source without one is left out by the caller,
+    as the reference skips it).
+    Returns dict(image (3,Hb,Wb), masks (M,Hb,Wb), boxes (M,4), labels (M), valid uint8 (M)) on the device, M = sum m_i, (Hb, Wb) the
+    largest source size: the accumulator is the rows with valid == 1, in order; nothing is read back here."""
+    S = len(sources)
+    if not 2 <= S <= SELF_COPY_MAX_SRC:
+        raise ValueError("self_copy_merge: %d sources, 2 to %d are built" % (S, SELF_COPY_MAX_SRC))
+    dev = sources[0][0].device
+    images = [s[0].contiguous() for s in sources]
+    masks = [s[1].contiguous() for s in sources]
+    counts = np.array([int(mk.shape[0]) for mk in masks], dtype=np.int32)
+    sizes = np.array([[int(im.shape[1]), int(im.shape[2])] for im in images], dtype=np.int32)
+    for i, (im, mk, s) in enumerate(zip(images, masks, sources)):
+        if not 1 <= counts[i] <= SELF_COPY_MAX:
+            raise ValueError("self_copy_merge: source %d brings %d objects, 1 to %d are built" % (i, counts[i], SELF_COPY_MAX))
+        if tuple(mk.shape[1:]) != tuple(im.shape[1:]) or int(s[2].shape[0]) != counts[i] or int(s[3].shape[0]) != counts[i]:
+            raise ValueError("self_copy_merge: source %d: masks %s / boxes %s / labels %s do not match its image %s" % (
+                i, tuple(mk.shape), tuple(s[2].shape), tuple(s[3].shape), tuple(im.shape)))
+    M, Hb, Wb = int(counts.sum()), int(sizes[:, 0].max()), int(sizes[:, 1].max())
+    boxes = torch.cat([s[2].float().reshape(-1, 4) for s in sources]).contiguous()
+    labels = torch.cat([s[3].to(torch.int64) for s in sources])
+    ptrs = lambda ts: (L.c_p * S)(*[L.ptr(t) for t in ts])      # noqa: E731
+    out_image = torch.empty(3, Hb, Wb, dtype=torch.uint8, device=dev)
+    out_masks = torch.empty(M, Hb, Wb, dtype=torch.uint8, device=dev)
+    out_boxes = torch.empty(M, 4, dtype=torch.float32, device=dev)
+    out_valid = torch.empty(M, dtype=torch.uint8, device=dev)
+    work = torch.empty(int(L.lib().dgx_self_copy_merge_workspace_words(S, M, Hb, Wb)), dtype=torch.int32, device=dev)
+    L.check(L.lib().dgx_self_copy_merge(ptrs(images), ptrs(masks), counts.ctypes.data, sizes.ctypes.data, S, L.ptr(boxes), Hb, Wb,
+                                        L.ptr(out_image), L.ptr(out_masks), L.ptr(out_boxes), L.ptr(out_valid), L.ptr(work), L.stream()),
+            "dgx_self_copy_merge")
+    return dict(image=out_image, masks=out_masks, boxes=out_boxes, labels=labels, valid=out_valid)
+
+
+def self_copy_paste_multi(image, masks, boxes, labels, sources, lazy_masks=False):
+    """Simple Copy-Paste from several source images onto the destination (image, masks, boxes, labels: as self_copy_paste takes them):
+    self_copy_merge, ONE read-back of the M validity bytes and boxes (the sync copy_paste's `keep` costs as well), then self_copy_paste
+    with the accumulated planes as the source and the survivors as `sel`, on the canvas self_copy_canvas gives for their boxes.
+    sources: as self_copy_merge takes them, but any number >= 0 after the empty ones are dropped here: one source left is
+    self_copy_paste itself, none is its m == 0 case.  Returns self_copy_paste's dict."""
+    sources = [s for s in sources if int(s[1].shape[0])]
+    if len(sources) < 2:
+        if not sources:
+            return self_copy_paste(image, masks, boxes, labels, image, masks[:0], boxes[:0], labels[:0], [], lazy_masks=lazy_masks)
+        s_img, s_masks, s_boxes, s_labels = sources[0]
+        return self_copy_paste(image, masks, boxes, labels, s_img, s_masks, s_boxes, s_labels, np.arange(int(s_masks.shape[0])),
+                               lazy_masks=lazy_masks)
+    acc = self_copy_merge(sources)
+    host = torch.cat([acc["boxes"], acc["valid"].float().unsqueeze(1)], dim=1).cpu().numpy()      # the one read-back
+    sel = np.flatnonzero(host[:, 4])
+    canvas = self_copy_canvas(image.shape[-2:], host[sel, :4])
+    return self_copy_paste(image, masks, boxes, labels, acc["image"], acc["masks"], acc["boxes"], acc["labels"], sel, canvas_hw=canvas,
+                           lazy_masks=lazy_masks, merged=True)

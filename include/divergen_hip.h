@@ -405,6 +405,43 @@ int dgx_self_copy_paste(const uint8_t* dst_image, const uint8_t* dst_masks, cons
                         const int32_t* sel, int m, int H, int W, uint8_t* out_image, uint8_t* out_masks,
                         float* out_boxes, uint8_t* out_valid, int32_t* workspace, void* stream);
 
+/* Self copy-paste from several source images (INPUT.SCP_NUM_SRC > 1 with INPUT.SCP_MULTI_SRC): the temporary stages of
+ * CopyPaste.__call__, DG/divergen/data/transforms/custom_copypaste.py:274-297.  Source 0 is the accumulator; every further source t
+ * is pasted onto it by one step of the kind dgx_self_copy_paste does, on a TEMPORARY canvas (h_t, w_t) = the ceil of the largest
+ * y2 / x2 among the accumulator's current boxes (objects still valid) and source t's boxes (:343-353, is_tmp_dst) -- image sizes play
+ * no part.  All four arrays are cropped or zero-padded to that canvas and stay so: a pixel outside it is zero from then on.  An
+ * accumulator object is kept at a stage when every |box of its updated mask - its box after the stage before| <= 10 or more than
+ * 300 mask pixels are left; once dropped it stays dropped.  All S - 1 stages run on `stream` without a host round trip: each canvas is
+ * derived on the device from the boxes and validity the stage before left, and applied as a predicate.
+ *   S sources, 2 <= S <= 4 (DGX_SELF_COPY_MAX_SRC).  HOST arrays: images[i] u8 (3,h_i,w_i) and masks[i] u8 (m_i,h_i,w_i) 0/1 bytes
+ *   (device pointers; the m_i SELECTED planes of source i in paste order), counts[i] = m_i in [1, 99], sizes = (h_0,w_0,h_1,w_1,..).
+ *   boxes f32 (M,4) in DEVICE memory, M = sum m_i: the sources' own boxes back to back.  Sources without a selected object are left
+ *   out by the caller (the reference skips them).
+ *   (Hb, Wb) >= every (h_i, w_i): the size of the outputs.  Every canvas lies inside the largest box extent; where that exceeds
+ *   (Hb, Wb) no source has a pixel, so nothing is lost.
+ * Outputs, every byte written:
+ *   out_image u8 (3,Hb,Wb)    the accumulated image (zero outside the last canvas)
+ *   out_masks u8 (M,Hb,Wb)    row off_i + j: plane j of source i as the stages left it (bytes pass through)
+ *   out_boxes f32 (M,4)       objects of sources 0 .. S-2: box of the updated mask (x_min, y_min, x_max + 1, y_max + 1; zeros when
+ *                             empty); objects of the last source: their own box
+ *   out_valid u8 (M)          1 while the object has been kept at every stage; rows and boxes of dropped objects are unspecified
+ * The accumulator the reference would hand to its final paste = the valid rows in order; the caller reads out_valid / out_boxes back
+ * once and calls dgx_self_copy_paste_merged with them as the source.  Integer atomics only: bit-reproducible.
+ * workspace: i32, 16-byte aligned, dgx_self_copy_merge_workspace_words(S, M, Hb, Wb) words (0 for arguments it refuses).
+ * Errors: S outside [2, 4], m_i outside [1, 99], a size <= 0 or above (Hb, Wb), a NULL pointer, a misaligned workspace ->
+ * DGX_ERR_BAD_ARG, nothing launched.  Hb * Wb >= 2^31 -> DGX_ERR_UNSUPPORTED. */
+#define DGX_SELF_COPY_MAX_SRC 4
+int64_t dgx_self_copy_merge_workspace_words(int S, int M, int Hb, int Wb);
+int dgx_self_copy_merge(const uint8_t* const* images, const uint8_t* const* masks, const int32_t* counts, const int32_t* sizes, int S,
+                        const float* boxes, int Hb, int Wb, uint8_t* out_image, uint8_t* out_masks, float* out_boxes,
+                        uint8_t* out_valid, int32_t* workspace, void* stream);
+
+/* dgx_self_copy_paste for a source that came out of dgx_self_copy_merge: the same step, m <= 99 * DGX_SELF_COPY_MAX_SRC. */
+int dgx_self_copy_paste_merged(const uint8_t* dst_image, const uint8_t* dst_masks, const float* dst_boxes0, int n0, int h1, int w1,
+                               const uint8_t* src_image, const uint8_t* src_masks, int ns, int hs, int ws,
+                               const int32_t* sel, int m, int H, int W, uint8_t* out_image, uint8_t* out_masks,
+                               float* out_boxes, uint8_t* out_valid, int32_t* workspace, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Fused parameter update over a flat arena: per-element gradient value clip, AdamW, EMA lerp of
  * the PRE-step weights (the reference updates the EMA before optimizer.step: DG/train_net.py:262-284),

@@ -1,11 +1,13 @@
 """Time the self copy-paste kernels (dgx_self_copy_paste) on the 1024 x 1024 case of tests/test_gpu_self_copy.py (n0 = 20 destination
 objects, ns = 40 source objects, m = 25 selected) next to the pool compositor (dgx_copy_paste, n0 = 10, K = 19: the problem of
-tools/compositor_modes_bench.py) in the same process.  Device-event timing around `--iters` calls after `--warmup`; one JSON line.
+tools/compositor_modes_bench.py) in the same process, and next to the same paste from S = 2 and S = 3 source images of that frame
+(layers.self_copy_paste_multi: dgx_self_copy_merge, the read-back of validity and boxes, dgx_self_copy_paste_merged; every source
+brings m = 25 objects), in milliseconds per sample.  Device-event timing around `--iters` calls after `--warmup`; one JSON line.
 
     python tools/self_copy_bench.py [--iters 100] [--out FILE]
     rocprofv3 --kernel-trace --stats -d DIR -o selfcopy -- python tools/self_copy_bench.py --iters 50
 
-The outputs are checked against tests/_selfcopy_ref.py once before timing (a wrong kernel is not timed).  Algorithmic bytes of one
+The outputs are checked against tests/_selfcopy_ref.py / _selfcopy_multi_ref.py once before timing (a wrong kernel is not timed).  Algorithmic bytes of one
 self copy: (n0 + m) * H * W * 2 + 9 * H * W (every mask plane read and written once, two images read, one written)."""
 import argparse
 import json
@@ -29,6 +31,7 @@ def main():
     p.add_argument("--out", default=None)
     a = p.parse_args()
     assert torch.cuda.is_available(), "self_copy_bench needs a GPU"
+    import _selfcopy_multi_ref as MR
     import _selfcopy_ref as SR
     from compositor_modes_bench import problem
     from test_gpu_self_copy import _scene
@@ -43,13 +46,24 @@ def main():
     got = la.self_copy_paste(*d, *s, sel, canvas_hw=(size, size))
     for k in ("image", "masks", "boxes", "labels"):
         assert np.array_equal(got[k].cpu().numpy(), ref[k]), k
+    # S source images of the same frame, each with its own m selected objects (the first is the single source above)
+    more = [_scene(rng, m, size, size) for _ in range(2)]
+    multi = [[(src[0], src[1][sel], src[2][sel], src[3][sel])] + more[:k] for k in (1, 2)]
+    multi_dev = [[tuple(torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in sc) for sc in srcs] for srcs in multi]
+    for srcs, srcs_dev in zip(multi, multi_dev):
+        ref = MR.self_copy_multi(*dst, srcs)
+        got = la.self_copy_paste_multi(*d, srcs_dev)
+        for k in ("image", "masks", "boxes", "labels"):
+            assert np.array_equal(got[k].cpu().numpy(), ref[k]), (len(srcs), k)
     img, masks, boxes, labels, pastes = problem()
     c = [torch.from_numpy(x).to(dev) for x in (img, masks, boxes, labels)]
     pk = pack_pastes(pastes, dev)
     calls = {"self_copy": lambda: la.self_copy_paste(*d, *s, sel, canvas_hw=(size, size), lazy_masks=True),
+             "self_copy_s2": lambda: la.self_copy_paste_multi(*d, multi_dev[0], lazy_masks=True),
+             "self_copy_s3": lambda: la.self_copy_paste_multi(*d, multi_dev[1], lazy_masks=True),
              "copy_paste_k19": lambda: la.copy_paste(*c, pk, lazy_masks=True)}
     nbytes = (n0 + m) * size * size * 2 + 9 * size * size
-    res = {"what": "1 image 1024x1024; self copy n0=20 ns=40 m=25; pool compositor n0=10 K=19; ms per call (device events, %d calls)" % a.iters,
+    res = {"what": "1 image 1024x1024; self copy n0=20 ns=40 m=25 (s2 / s3: merge + read-back + paste from 2 / 3 sources of m=25 each); pool compositor n0=10 K=19; ms per call (device events, %d calls)" % a.iters,
            "self_copy_algorithmic_bytes": nbytes}
     for name, fn in calls.items():
         for _ in range(a.warmup):
