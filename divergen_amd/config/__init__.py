@@ -165,6 +165,12 @@ def get_cfg():
     #   on the device first (divergen_amd/csrc/self_copy_merge.hip), which costs one more read-back of validity bytes and boxes per
     #   sample; without the key SCP_NUM_SRC != 1 is refused at start-up.
     cfg.INPUT.SCP_MULTI_SRC = False
+    #   INPUT.SCP_SRC_MODES: admits, to the self-copy methods of INPUT.USE_COPY_METHOD, INPUT.SCP_TYPE 'in_domain' / 'cas' / 'the_cls' /
+    #   'the_cls_img' (the source image drawn per category) and INPUT.SCP_SRC_OBJ_SELECT False (every object of the source is pasted:
+    #   dgx_self_copy_paste_all, no bound of 99), and makes INPUT.RM_BG_PROB > 0 remove the destination's background under EVERY copy
+    #   method, as the reference does (divergen_amd/csrc/remove_background.hip); without the key the first two are refused at start-up
+    #   and RM_BG_PROB is refused with a self-copy method and ignored otherwise.
+    cfg.INPUT.SCP_SRC_MODES = False
     #   SOLVER.ALLREDUCE_DTYPE: "fp32" (the reference's DDP: gradients all-reduced as they are) or "bf16" (gradient buckets go over
     #   xGMI as bf16, half the bytes per step; engine/ddp.py ArenaReducer(wire_dtype=...)).
     cfg.SOLVER.ALLREDUCE_DTYPE = "fp32"

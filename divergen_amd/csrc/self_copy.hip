@@ -28,7 +28,7 @@ __global__ __launch_bounds__(256) void sc_source_kernel(const uint8_t* __restric
                                                         uint32_t* __restrict__ composed) {
     __shared__ int32_t s_sel[SC_MAX_M];
     const int ja = blockIdx.y * per_group, jb = min(m, ja + per_group);
-    for (int j = ja + threadIdx.x; j < jb; j += blockDim.x) s_sel[j - ja] = sel[j];
+    for (int j = ja + threadIdx.x; j < jb; j += blockDim.x) s_sel[j - ja] = sel ? sel[j] : j;      // no sel: plane j itself (paste-all)
     __syncthreads();
     const int64_t HW = (int64_t)H * W, shw = (int64_t)hs * ws, nchunk = (int64_t)H * ncx;
     for (int64_t ci = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; ci < nchunk; ci += (int64_t)gridDim.x * blockDim.x) {
@@ -111,17 +111,24 @@ __global__ void sc_resolve_kernel(const int32_t* __restrict__ stats, const float
     out_valid[obj] = (m == 0 || ok) ? 1 : 0;
 }
 
-// max_m: 99 for one source image; 99 per merged source when the planes come out of dgx_self_copy_merge
+// max_m: 99 for one source image; 99 per merged source when the planes come out of dgx_self_copy_merge.  ident: the paste-all entry --
+// sel is not read (plane j is source plane j), m == ns, and m is bounded by the grid and the 64-bit plane offsets alone.
 static int sc_paste(const uint8_t* dst_image, const uint8_t* dst_masks, const float* dst_boxes0, int n0, int h1, int w1,
                     const uint8_t* src_image, const uint8_t* src_masks, int ns, int hs, int ws, const int32_t* sel, int m, int max_m,
-                    int H, int W, uint8_t* out_image, uint8_t* out_masks, float* out_boxes, uint8_t* out_valid, int32_t* workspace,
+                    bool ident, int H, int W, uint8_t* out_image, uint8_t* out_masks, float* out_boxes, uint8_t* out_valid, int32_t* workspace,
                     void* stream) {
     if (n0 < 0 || ns < 0 || m < 0 || m > max_m || h1 <= 0 || w1 <= 0 || H < h1 || W < w1 || (m > 0 && (ns <= 0 || hs <= 0 || ws <= 0)))
         return DGX_ERR_BAD_ARG;
     if (!dst_image || !out_image || !workspace || ((uintptr_t)workspace & 15) || (n0 > 0 && (!dst_masks || !dst_boxes0 || !out_boxes || !out_valid)) ||
-        (m > 0 && (!src_image || !src_masks || !sel)) || (n0 + m > 0 && !out_masks))
+        (m > 0 && (!src_image || !src_masks || (!sel && !ident))) || ((int64_t)n0 + m > 0 && !out_masks))
         return DGX_ERR_BAD_ARG;
     if ((int64_t)H * W >= ((int64_t)1 << 31)) return DGX_ERR_UNSUPPORTED;
+    if (ident) {
+        // grid.y = ceil(m / per) with per <= SC_MAX_M whatever the frame; rows n0 .. n0 + m - 1 of out_masks as int, their bytes as int64
+        const int64_t rows = (int64_t)n0 + m;
+        if (((int64_t)m + SC_MAX_M - 1) / SC_MAX_M > 65535 || rows > 0x7fffffff || rows > INT64_MAX / ((int64_t)H * W)) return DGX_ERR_UNSUPPORTED;
+        sel = nullptr;
+    }
     hipStream_t st = (hipStream_t)stream;
     if (m == 0) { hs = 0; ws = 0; }                // the source is never read
     const int ncx = (W + SCX - 1) / SCX;
@@ -141,7 +148,7 @@ static int sc_paste(const uint8_t* dst_image, const uint8_t* dst_masks, const fl
     if (m > 0) {
         const int groups = want < m ? want : m;
         int per = (m + groups - 1) / groups;
-        if (per > SC_MAX_M) per = SC_MAX_M;          // s_sel holds one group's indices (only a merged source has m > 99)
+        if (per > SC_MAX_M) per = SC_MAX_M;          // s_sel holds one group's indices (only a merged or a paste-all source has m > 99)
         hipLaunchKernelGGL(sc_source_kernel, dim3(gx, (m + per - 1) / per), dim3(256), 0, st, src_masks, ns, hs, ws, sel, m, per, n0,
                            H, W, ncx, fl, out_masks, composed);
     }
@@ -164,7 +171,7 @@ extern "C" int dgx_self_copy_paste(const uint8_t* dst_image, const uint8_t* dst_
                                    const uint8_t* src_image, const uint8_t* src_masks, int ns, int hs, int ws,
                                    const int32_t* sel, int m, int H, int W, uint8_t* out_image, uint8_t* out_masks,
                                    float* out_boxes, uint8_t* out_valid, int32_t* workspace, void* stream) {
-    return sc_paste(dst_image, dst_masks, dst_boxes0, n0, h1, w1, src_image, src_masks, ns, hs, ws, sel, m, SC_MAX_M, H, W, out_image,
+    return sc_paste(dst_image, dst_masks, dst_boxes0, n0, h1, w1, src_image, src_masks, ns, hs, ws, sel, m, SC_MAX_M, false, H, W, out_image,
                     out_masks, out_boxes, out_valid, workspace, stream);
 }
 
@@ -172,6 +179,15 @@ extern "C" int dgx_self_copy_paste_merged(const uint8_t* dst_image, const uint8_
                                           const uint8_t* src_image, const uint8_t* src_masks, int ns, int hs, int ws,
                                           const int32_t* sel, int m, int H, int W, uint8_t* out_image, uint8_t* out_masks,
                                           float* out_boxes, uint8_t* out_valid, int32_t* workspace, void* stream) {
-    return sc_paste(dst_image, dst_masks, dst_boxes0, n0, h1, w1, src_image, src_masks, ns, hs, ws, sel, m, SC_MAX_M * SCM_MAX_SRC, H, W,
+    return sc_paste(dst_image, dst_masks, dst_boxes0, n0, h1, w1, src_image, src_masks, ns, hs, ws, sel, m, SC_MAX_M * SCM_MAX_SRC, false, H, W,
+                    out_image, out_masks, out_boxes, out_valid, workspace, stream);
+}
+
+// every plane of the source in order (CopyPaste(selected=False)): no sel, no bound of 99
+extern "C" int dgx_self_copy_paste_all(const uint8_t* dst_image, const uint8_t* dst_masks, const float* dst_boxes0, int n0, int h1, int w1,
+                                       const uint8_t* src_image, const uint8_t* src_masks, int ns, int hs, int ws, int H, int W,
+                                       uint8_t* out_image, uint8_t* out_masks, float* out_boxes, uint8_t* out_valid, int32_t* workspace,
+                                       void* stream) {
+    return sc_paste(dst_image, dst_masks, dst_boxes0, n0, h1, w1, src_image, src_masks, ns, hs, ws, nullptr, ns, 0x7fffffff, true, H, W,
                     out_image, out_masks, out_boxes, out_valid, workspace, stream);
 }

@@ -459,13 +459,21 @@ class CopyPasteMapper:
     no mix results in that configuration, so SimpleCopyPaste returns its input (custom_copypaste.py:254-259).
     USE_COPY_METHOD 'self_copy' / 'both' / 'p:<f>' (mapper.py:884-936): Simple Copy-Paste from a second training image
     (custom_copypaste.py:242-341), worker half in _call_self_copy, pixels in dgx_self_copy_paste (_finish_self_copy); with
-    INPUT.SCP_MULTI_SRC from INPUT.SCP_NUM_SRC <= 4 images, merged by dgx_self_copy_merge first."""
+    INPUT.SCP_MULTI_SRC from INPUT.SCP_NUM_SRC <= 4 images, merged by dgx_self_copy_merge first.
+    With INPUT.SCP_SRC_MODES: INPUT.SCP_TYPE 'in_domain' / 'cas' / 'the_cls' / 'the_cls_img' (mapper.py:782-815, :829-835: the source
+    drawn per category, _class_sources), a source pasted whole (mapper.py:764-765: dgx_self_copy_paste_all) and INPUT.RM_BG_PROB
+    (mapper.py:869-872, under every copy method: dgx_remove_background in finish)."""
+
+    SCP_TYPES = ("in_domain", "cas", "the_cls", "the_cls_img")
+    # what INPUT.SCP_SRC_MODES switches on; the defaults are what a mapper without the key does
+    scp_type, paste_all, rm_bg_prob, per_cat_map, select_cats = "", False, 0.0, None, ()
 
     def __init__(self, mapper, cfg):
         self.mapper = mapper
         self.use_scp = cfg.INPUT.USE_SCP
         self.num_src = cfg.INPUT.SCP_NUM_SRC
         self.method = cfg.INPUT.USE_COPY_METHOD
+        self.src_modes = bool(cfg.INPUT.get("SCP_SRC_MODES", False))
         self.inst_pool = None
         self.dataset = None
         self.pack = True               # one blob per sample across the process boundary (pack_sample); the loader's finish() unpacks
@@ -474,6 +482,12 @@ class CopyPasteMapper:
         self.self_only = self.method == "self_copy"
         if self.self_prob is not None:
             self._check_self_copy(cfg)
+        if self.src_modes:
+            self._check_rm_bg(cfg)
+            self.rm_bg_prob = max(float(cfg.INPUT.RM_BG_PROB), 0.0)
+            if self.self_prob is not None:
+                self.scp_type, self.select_cats = cfg.INPUT.SCP_TYPE, list(cfg.INPUT.SCP_SELECT_CATS_LIST)
+                self.paste_all = self._pastes_all(cfg.INPUT) is not None
         if cfg.INPUT.INST_POOL and self.method != "none" and not self.self_only:
             from .copypaste import InstPool
             if cfg.INPUT.INST_POOL_SAMPLE_TYPE != "cas_random" or cfg.INPUT.INST_POOL_FORMAT != "RGBA":
@@ -508,20 +522,24 @@ class CopyPasteMapper:
     def _check_self_copy(cfg):
         """The self-copy branch is built for SCP_TYPE '', one source image (up to SELF_COPY_MAX_SRC with this build's key
         INPUT.SCP_MULTI_SRC), selected objects, 'basic' blend (the reference's own choice, mapper.py:770); every other switch of that
-        branch is refused by name."""
+        branch is refused by name.  This build's key INPUT.SCP_SRC_MODES admits SCP_TYPE 'in_domain' / 'cas' / 'the_cls' /
+        'the_cls_img', SCP_SRC_OBJ_SELECT False and RM_BG_PROB in (0, 1] (_check_src_modes, _check_rm_bg)."""
         from ..layers.copy_paste import SELF_COPY_MAX_SRC
         inp = cfg.INPUT
+        modes = bool(inp.get("SCP_SRC_MODES", False))
+        if modes:
+            CopyPasteMapper._check_src_modes(cfg)
         if bool(inp.get("SCP_MULTI_SRC", False)) and not 1 <= inp.SCP_NUM_SRC <= SELF_COPY_MAX_SRC:
             raise NotImplementedError("INPUT.SCP_NUM_SRC {!r} with INPUT.USE_COPY_METHOD '{}': INPUT.SCP_MULTI_SRC merges 1 to {} source "
                                       "images (dgx_self_copy_merge)".format(inp.SCP_NUM_SRC, inp.USE_COPY_METHOD, SELF_COPY_MAX_SRC))
-        refused = [("SCP_TYPE", inp.SCP_TYPE != "", "only '' (a random training image as the source)"),
+        refused = [("SCP_TYPE", inp.SCP_TYPE != "" and not modes, "only '' (a random training image as the source)"),
                    ("SCP_NUM_SRC", inp.SCP_NUM_SRC != 1 and not bool(inp.get("SCP_MULTI_SRC", False)),
                     "only 1 (several sources are merged on a temporary canvas first)"),
-                   ("SCP_SRC_OBJ_SELECT", not inp.SCP_SRC_OBJ_SELECT, "only True"),
+                   ("SCP_SRC_OBJ_SELECT", not inp.SCP_SRC_OBJ_SELECT and not modes, "only True"),
                    ("BLANK_RATIO", inp.BLANK_RATIO > 0, "the source is not resized (needs cv2.resize)"),
                    ("ROTATE_SRC", bool(inp.ROTATE_SRC), "the source is not rotated"),
                    ("LIMIT_SRC_LSJ", bool(inp.LIMIT_SRC_LSJ), "the source takes the mapper's default augmentations"),
-                   ("RM_BG_PROB", inp.RM_BG_PROB > 0, "background removal is not built"),
+                   ("RM_BG_PROB", inp.RM_BG_PROB > 0 and not modes, "background removal is not built"),
                    ("SCP_RFS", bool(inp.SCP_RFS), "the source index is drawn uniformly"),
                    ("USE_INSTABOOST", bool(inp.USE_INSTABOOST), "InstaBoost is not built"),
                    ("USE_COLOR_JITTER", bool(inp.USE_COLOR_JITTER), "colour jitter is not built")]
@@ -532,8 +550,56 @@ class CopyPasteMapper:
             raise NotImplementedError("INPUT.ACTIVE_SELECT with INPUT.USE_COPY_METHOD '{}': BSGAL's origin / held-out samples are built "
                                       "for 'syn_copy' only".format(inp.USE_COPY_METHOD))
 
+    @staticmethod
+    def _pastes_all(inp):
+        """The key that makes the source paste whole -- CopyPaste(selected=SCP_SRC_OBJ_SELECT and scp_type not in ('in_domain', 'cas')),
+        mapper.py:764-765 -- or None when _select_object runs."""
+        if inp.SCP_TYPE in ("in_domain", "cas"):
+            return "SCP_TYPE"
+        return None if inp.SCP_SRC_OBJ_SELECT else "SCP_SRC_OBJ_SELECT"
+
+    @staticmethod
+    def _check_src_modes(cfg):
+        """What INPUT.SCP_SRC_MODES still refuses of the switches it admits to a self-copy method."""
+        inp = cfg.INPUT
+        t = inp.SCP_TYPE
+        if t in ("rc_only", "f_only"):
+            raise NotImplementedError("INPUT.SCP_TYPE {!r} with INPUT.USE_COPY_METHOD '{}': the reference's own mapper has no branch for it "
+                                      "and raises NotImplementedError at the first sample (mapper.py:892-916); INPUT.SCP_SRC_MODES builds "
+                                      "'', {}".format(t, inp.USE_COPY_METHOD, ", ".join(repr(x) for x in CopyPasteMapper.SCP_TYPES)))
+        if t != "" and t not in CopyPasteMapper.SCP_TYPES:
+            raise NotImplementedError("INPUT.SCP_TYPE {!r} with INPUT.USE_COPY_METHOD '{}': INPUT.SCP_SRC_MODES builds '', {}".format(
+                t, inp.USE_COPY_METHOD, ", ".join(repr(x) for x in CopyPasteMapper.SCP_TYPES)))
+        if t in ("the_cls", "the_cls_img") and len(inp.SCP_SELECT_CATS_LIST) < max(int(inp.SCP_NUM_SRC), 1):
+            raise ValueError("INPUT.SCP_SELECT_CATS_LIST {!r} with INPUT.SCP_TYPE {!r}: INPUT.SCP_NUM_SRC {} categories are drawn from it "
+                             "without replacement per sample".format(list(inp.SCP_SELECT_CATS_LIST), t, inp.SCP_NUM_SRC))
+        whole = CopyPasteMapper._pastes_all(inp)
+        if whole is not None and inp.SCP_NUM_SRC > 1:
+            raise NotImplementedError("INPUT.SCP_NUM_SRC {!r} with INPUT.{} {!r}: a source pasted whole is built for one source image "
+                                      "(dgx_self_copy_merge takes at most 99 objects per source)".format(inp.SCP_NUM_SRC, whole, inp[whole]))
+
+    @staticmethod
+    def _check_rm_bg(cfg):
+        """INPUT.RM_BG_PROB under INPUT.SCP_SRC_MODES, whatever the copy method (the reference draws it before `if self.use_scp`)."""
+        inp = cfg.INPUT
+        if inp.RM_BG_PROB > 1:
+            raise ValueError("INPUT.RM_BG_PROB {!r}: a probability, at most 1 (the reference asserts it at the first sample, "
+                             "mapper.py:870)".format(inp.RM_BG_PROB))
+        if inp.RM_BG_PROB > 0 and bool(inp.get("ACTIVE_SELECT", False)):
+            raise NotImplementedError("INPUT.RM_BG_PROB {!r} with INPUT.ACTIVE_SELECT: background removal is built for DiverGen's mapper; "
+                                      "BSGAL's is a different file".format(inp.RM_BG_PROB))
+
     def set_dataset(self, dataset):
         self.dataset = dataset
+        if self.scp_type in self.SCP_TYPES:
+            # mapper.py:829-835: image indices per category, categories in order of first appearance ('cas' draws from the keys)
+            self.per_cat_map = {}
+            for i, d in enumerate(dataset):
+                for cid in set([a["category_id"] for a in d.get("annotations", [])]):
+                    self.per_cat_map.setdefault(cid, []).append(i)
+            if self.scp_type == "cas" and len(self.per_cat_map) < self.num_src:
+                raise ValueError("INPUT.SCP_TYPE 'cas' with INPUT.SCP_NUM_SRC {}: the training set shows {} categories".format(
+                    self.num_src, len(self.per_cat_map)))
         if self.active_select:
             pool = {}
             for i, d in enumerate(dataset):
@@ -570,6 +636,8 @@ class CopyPasteMapper:
         result = self.mapper(dataset_dict)
         if "instances" not in result or not result["instances"].has("gt_masks"):        # mapper.py:862-864
             return result
+        if self.rm_bg_prob > 0 and np.random.uniform(0.0, 1.0) <= self.rm_bg_prob:      # mapper.py:869-872; the pixels: finish()
+            result = dict(result, rm_bg=True)
         idxs = []
         if self.use_scp and self.dataset is not None:
             idxs = [np.random.randint(0, len(self.dataset)) for _ in range(self.num_src)]
@@ -592,22 +660,34 @@ class CopyPasteMapper:
         masks / boxes / labels in paste order and the canvas size -- what dgx_self_copy_paste needs; the training process runs it
         (finish).  With INPUT.SCP_NUM_SRC > 1 the sources that selected nothing are skipped as the reference skips them; one left is
         the case above, byte for byte; two or more make `scp_src` a LIST of such groups (no canvas: it follows from the merge), each
-        cropped to the largest box extent of all of them, beyond which no stage's canvas reaches."""
+        cropped to the largest box extent of all of them, beyond which no stage's canvas reaches.
+        INPUT.SCP_SRC_MODES: the sources of an INPUT.SCP_TYPE come from _class_sources instead (the index draws above stay consumed,
+        :877); a source pasted whole makes no selection draw and ships all its objects in their order, marked `all` for finish; no source
+        at all ('in_domain' on a destination without instances) leaves the sample without `scp_src`: CopyPaste.__call__ returns its
+        input untouched then (custom_copypaste.py:257-259), Instances not rebuilt."""
         from ..layers.copy_paste import self_copy_canvas
         take_self, take_syn = True, self.method == "both"
         if self.method.startswith("p:"):
             take_self = np.random.rand() < self.self_prob
             take_syn = not take_self
-        srcs = [self.mapper(self.dataset[i]) for i in idxs] if take_self else []
+        if not take_self:
+            srcs = []
+        elif self.scp_type == "":
+            srcs = [self.mapper(self.dataset[i]) for i in idxs]
+        else:
+            srcs = self._class_sources(result)
         if take_syn and self.inst_pool is not None:
             result = self.inst_pool.prepare(result)
-        if take_self:
+        if take_self and srcs:
             result = dict(result)
             picked = []                                        # (source, selected indices) of the sources that selected something
             for src in srcs:
                 ns = len(src["instances"])
-                m = np.random.randint(0, min(ns + 1, 100))
-                sel = np.random.choice(ns, size=m, replace=False)
+                if self.paste_all:                             # CopyPaste(selected=False): no draw
+                    m, sel = ns, np.arange(ns)
+                else:
+                    m = np.random.randint(0, min(ns + 1, 100))
+                    sel = np.random.choice(ns, size=m, replace=False)
                 if m:
                     picked.append((src, torch.from_numpy(np.asarray(sel, dtype=np.int64))))
             h1, w1 = result["image"].shape[-2:]
@@ -622,6 +702,8 @@ class CopyPasteMapper:
                 src, sel_t = picked[0]
                 H, W = self_copy_canvas((h1, w1), src["instances"].gt_boxes.tensor[sel_t])
                 result["scp_src"] = dict(group(src, sel_t, H, W), hw=(H, W))
+                if self.paste_all:
+                    result["scp_src"]["all"] = True
             elif picked:
                 H, W = self_copy_canvas((0, 0), torch.cat([src["instances"].gt_boxes.tensor[sel_t] for src, sel_t in picked]))
                 result["scp_src"] = [group(src, sel_t, H, W) for src, sel_t in picked]
@@ -635,13 +717,36 @@ class CopyPasteMapper:
             result["scp_file_name"] = srcs[0].get("file_name") if len(srcs) == 1 else [src.get("file_name") for src in srcs]
         return pack_sample(result) if self.pack else result
 
+    def _class_sources(self, result):
+        """_filter_in_specific_cls (mapper.py:782-815) in its np.random order: the categories -- 'in_domain': num_src draws among the
+        destination's own classes (none: no source, no draw); 'cas' / 'the_cls*': choice without replacement among the categories of the
+        training set / INPUT.SCP_SELECT_CATS_LIST -- then per source one image of that category's list, a deep copy of its dict with the
+        annotations filtered to the class list (not for 'the_cls_img'), through the mapper with its own draws."""
+        t = self.scp_type
+        if t == "in_domain":
+            cls_list = list(set(result["instances"].gt_classes.tolist()))
+            cats_pool = [self.per_cat_map.get(c, []) for c in cls_list]
+            if len(cats_pool) == 0:
+                return []
+            pools = [cats_pool[np.random.randint(0, len(cats_pool))] for _ in range(self.num_src)]
+        else:
+            cls_list = np.random.choice(list(self.per_cat_map.keys()) if t == "cas" else self.select_cats, self.num_src, replace=False)
+            pools = [self.per_cat_map.get(c, []) for c in cls_list]
+        srcs = []
+        for pool in pools:
+            d = copy.deepcopy(self.dataset[pool[np.random.randint(0, len(pool))]])
+            if t != "the_cls_img":
+                d["annotations"] = [a for a in d["annotations"] if a["category_id"] in cls_list]
+            srcs.append(self.mapper(d))
+        return srcs
+
     @staticmethod
     def _finish_self_copy(out, scp, dev):
         """Training-process half of the self copy: ONE dgx_self_copy_paste call on the current stream (a list of source groups:
         layers.self_copy_paste_multi -- dgx_self_copy_merge, one read-back, dgx_self_copy_paste_merged), then the Instances rebuilt with
         gt_boxes / gt_classes / gt_masks only (custom_copypaste.py:311-318: instance_source and every other field are gone, also
-        when nothing was pasted)."""
-        from ..layers.copy_paste import self_copy_paste, self_copy_paste_multi
+        when nothing was pasted).  A source pasted whole (`all`): dgx_self_copy_paste_all, any number of objects."""
+        from ..layers.copy_paste import self_copy_paste, self_copy_paste_all, self_copy_paste_multi
         from .copypaste import result_instances
         if dev.type != "cuda":
             raise RuntimeError("INPUT.USE_COPY_METHOD with a self copy needs the GPU compositor (dgx_self_copy_paste); device is %s" % dev)
@@ -650,6 +755,9 @@ class CopyPasteMapper:
         dst = (out["image"], inst.gt_masks.tensor.view(torch.uint8), inst.gt_boxes.tensor, inst.gt_classes)
         if isinstance(scp, list):      # several sources (INPUT.SCP_MULTI_SRC): dgx_self_copy_merge, one read-back, then the paste
             r = self_copy_paste_multi(*dst, [tuple(up(g[k]) for k in ("image", "masks", "boxes", "labels")) for g in scp], lazy_masks=True)
+        elif scp.get("all"):
+            r = self_copy_paste_all(*dst, up(scp["image"]), up(scp["masks"]), up(scp["boxes"]), up(scp["labels"]), canvas_hw=scp["hw"],
+                                    lazy_masks=True)
         else:
             m = int(scp["labels"].shape[0])
             r = self_copy_paste(*dst, up(scp["image"]), up(scp["masks"]), up(scp["boxes"]), up(scp["labels"]), np.arange(m),
@@ -658,16 +766,34 @@ class CopyPasteMapper:
         out["image"], (out["height"], out["width"]) = r["image"], out["instances"].image_size
         return out
 
+    @staticmethod
+    def _finish_rm_bg(result, dev, own):
+        """Training-process half of INPUT.RM_BG_PROB (mapper.py:869-872): the image and the masks go up and ONE dgx_remove_background
+        call on the current stream blanks what no mask covers -- before the pool compositor and the self copy, which then find both on
+        the device.  own: the uploaded image is this call's own copy and is rewritten in place."""
+        from ..layers.copy_paste import remove_background
+        if dev.type != "cuda":
+            raise RuntimeError("INPUT.RM_BG_PROB needs the GPU kernel (dgx_remove_background); device is %s" % dev)
+        result = {k: v for k, v in result.items() if k != "rm_bg"}
+        own = own or not result["image"].is_cuda
+        image, inst = result["image"].to(dev, non_blocking=True), result["instances"].to(dev)
+        result["image"] = remove_background(image, inst.gt_masks.tensor.view(torch.uint8), out=image if own and image.is_contiguous() else None)
+        result["instances"] = inst
+        return result
+
     def finish(self, result, device):
         """What the TRAINING PROCESS runs on one worker result, on the current stream: upload (asynchronous from pinned memory) and
         the compositor kernel; with INPUT.ACTIVE_SELECT the un-pasted sample stays available as origin_* (it is the uploaded
         input: the compositor writes a copy)."""
         from .copypaste import InstPool
         dev = torch.device(device)
+        own = "blob" in result                       # the sample's tensors come out of a device copy made here
         result = unpack_sample(result, dev, self.ring)
         if "instances" not in result:
             result["image"] = result["image"].to(dev, non_blocking=True)
             return result
+        if result.get("rm_bg"):
+            result = self._finish_rm_bg(result, dev, own)
         if "paste_pack" in result and dev.type == "cuda":
             out = InstPool.composite(result, dev)
             img, gm, gb, gc = out.pop("_uploaded")
@@ -740,6 +866,8 @@ def pack_sample(d):
         out["blob_scp_n"] = len(d["scp_src"])
     elif "scp_src" in d:
         out["blob_scp_hw"] = tuple(int(v) for v in d["scp_src"]["hw"])
+        if d["scp_src"].get("all"):                  # a source pasted whole (INPUT.SCP_SRC_MODES): finish calls dgx_self_copy_paste_all
+            out["blob_scp_all"] = True
     if "paste_pack" in d:
         out["blob_K"] = int(d["paste_pack"]["K"])
     modes = d["paste_pack"].get("modes") if "paste_pack" in d else None
@@ -791,6 +919,8 @@ def unpack_sample(d, device, ring=None):
     if "scp_image" in f:
         out["scp_src"] = {"image": f["scp_image"], "masks": f["scp_masks"], "boxes": f["scp_boxes"], "labels": f["scp_labels"],
                           "hw": tuple(d["blob_scp_hw"])}
+        if d.get("blob_scp_all"):
+            out["scp_src"]["all"] = True
     if d.get("blob_scp_n"):
         out["scp_src"] = [{k: f["scp%d_%s" % (i, k)] for k in ("image", "masks", "boxes", "labels")} for i in range(d["blob_scp_n"])]
     return out

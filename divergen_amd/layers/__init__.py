@@ -7,5 +7,5 @@ from .window_ops import window_attention_core, window_gather, window_scatter, sh
 from .roi_ops import roi_align, roi_pooler, mask_crop  # noqa
 from .box_ops import nms, batched_nms, iou_match, nms_batched_sorted  # noqa
 from .dense_ops import centernet_targets  # noqa
-from .copy_paste import PackedPastes, check_poisson_report, copy_paste, pack_pastes, pack_pastes_host, poisson_blend, self_copy_canvas, self_copy_merge, self_copy_paste, self_copy_paste_multi  # noqa
+from .copy_paste import PackedPastes, check_poisson_report, copy_paste, pack_pastes, pack_pastes_host, poisson_blend, remove_background, self_copy_canvas, self_copy_merge, self_copy_paste, self_copy_paste_all, self_copy_paste_multi  # noqa
 from .optim_ops import adamw_ema_step, clip_coef, sgd_ema_step  # noqa

@@ -1,6 +1,7 @@
 """Instance copy-paste compositor on the GPU: the 'basic', 'alpha', 'gaussian' and (opt-in) 'possion' blends of all K pastes of an
 image in one libdgx call (copy_paste), one 'possion' paste alone (poisson_blend), the self copy between two real images
-(self_copy_paste) and from several source images (self_copy_merge, self_copy_paste_multi).  Reference: DG/divergen/data/custom_build_copypaste_mapper.py:488-566, :79-92; custom_cp_method.py:5-18."""
+(self_copy_paste; self_copy_paste_all for a source pasted whole) and from several source images (self_copy_merge, self_copy_paste_multi),
+background removal (remove_background).  Reference: DG/divergen/data/custom_build_copypaste_mapper.py:488-566, :79-92; custom_cp_method.py:5-18."""
 import numpy as np
 import torch
 
@@ -242,7 +243,6 @@ def self_copy_paste(image, masks, boxes, labels, src_image, src_masks, src_boxes
     dev = image.device
     sel = np.asarray(sel, dtype=np.int64).reshape(-1)
     m, n0, ns = int(sel.shape[0]), int(masks.shape[0]), int(src_masks.shape[0])
-    h1, w1 = int(image.shape[1]), int(image.shape[2])
     entry, most = ("dgx_self_copy_paste_merged", SELF_COPY_MAX * SELF_COPY_MAX_SRC) if merged else ("dgx_self_copy_paste", SELF_COPY_MAX)
     if m > most:
         raise ValueError("self_copy_paste: %d source objects selected, at most %d" % (m, most))
@@ -255,6 +255,16 @@ def self_copy_paste(image, masks, boxes, labels, src_image, src_masks, src_boxes
         return out
     sel_t = upload_i32(sel, dev)
     sel_boxes = src_boxes.float().index_select(0, sel_t.long())
+    sel_labels = src_labels.to(torch.int64).index_select(0, sel_t.long())
+    return _self_copy_step(entry, image, masks, boxes, labels, src_image, src_masks, sel_t, sel_boxes, sel_labels, canvas_hw, lazy_masks)
+
+
+def _self_copy_step(entry, image, masks, boxes, labels, src_image, src_masks, sel_t, sel_boxes, sel_labels, canvas_hw, lazy_masks):
+    """The libdgx call of self_copy_paste (sel_t: the m selected planes, int32 on the device) and self_copy_paste_all (sel_t None: every
+    plane of the source in order) and the ONE compaction after it.  sel_boxes / sel_labels: the m pasted objects' own, m > 0."""
+    dev = image.device
+    m, n0, ns = int(sel_boxes.shape[0]), int(masks.shape[0]), int(src_masks.shape[0])
+    h1, w1 = int(image.shape[1]), int(image.shape[2])
     H, W = (int(v) for v in canvas_hw) if canvas_hw is not None else self_copy_canvas((h1, w1), sel_boxes)
     image, masks, boxes0 = image.contiguous(), masks.contiguous(), boxes.float().contiguous()
     src_image, src_masks = src_image.contiguous(), src_masks.contiguous()
@@ -267,14 +277,55 @@ def self_copy_paste(image, masks, boxes, labels, src_image, src_masks, src_boxes
     out_boxes = torch.empty(n0, 4, dtype=torch.float32, device=dev)
     out_valid = torch.empty(n0, dtype=torch.uint8, device=dev)
     work = torch.empty(((n0 * 5 + 3) & ~3) + H * ((W + 15) // 16) * 4, dtype=torch.int32, device=dev)
+    chosen = () if sel_t is None else (L.ptr(sel_t), m)
     L.check(getattr(L.lib(), entry)(L.ptr(image), L.ptr(masks) if n0 else None, L.ptr(boxes0) if n0 else None, n0, h1, w1,
-                                    L.ptr(src_image), L.ptr(src_masks), ns, hs, ws, L.ptr(sel_t), m, H, W,
+                                    L.ptr(src_image), L.ptr(src_masks), ns, hs, ws, *chosen, H, W,
                                     L.ptr(out_image), L.ptr(out_masks), L.ptr(out_boxes) if n0 else None,
                                     L.ptr(out_valid) if n0 else None, L.ptr(work), L.stream()), entry)
     keep = torch.cat([out_valid, torch.ones(m, dtype=torch.uint8, device=dev)]).nonzero().squeeze(1)      # ONE compaction
     all_boxes = torch.cat([out_boxes, sel_boxes])
-    all_labels = torch.cat([labels.to(torch.int64), src_labels.to(torch.int64).index_select(0, sel_t.long())])
+    all_labels = torch.cat([labels.to(torch.int64), sel_labels])
     return _compacted(out_image, out_masks, keep, lazy_masks, boxes=all_boxes, labels=all_labels)
+
+
+def self_copy_paste_all(image, masks, boxes, labels, src_image, src_masks, src_boxes, src_labels, canvas_hw=None, lazy_masks=False):
+    """self_copy_paste with EVERY object of the source, in its order, in ONE dgx_self_copy_paste_all call: what the reference's
+    CopyPaste(selected=False) pastes (INPUT.SCP_SRC_OBJ_SELECT False, INPUT.SCP_TYPE 'in_domain' / 'cas'; mapper.py:764-765,
+    custom_copypaste.py:282-283).  No `sel` and no bound of 99: that bound is _select_object's draw, a source pasted whole brings all its
+    ns objects.  Arguments and the returned dict as self_copy_paste; ns == 0: nothing is pasted, the inputs come back as they are."""
+    dev = image.device
+    n0, ns = int(masks.shape[0]), int(src_masks.shape[0])
+    if int(src_boxes.shape[0]) != ns or int(src_labels.shape[0]) != ns:
+        raise ValueError("self_copy_paste_all: %d source masks, %d boxes, %d labels" % (ns, int(src_boxes.shape[0]), int(src_labels.shape[0])))
+    if ns == 0:
+        out = dict(image=image, masks=masks, boxes=boxes, labels=labels)
+        if lazy_masks:
+            out["keep"] = torch.arange(n0, dtype=torch.int64, device=dev)
+        return out
+    return _self_copy_step("dgx_self_copy_paste_all", image, masks, boxes, labels, src_image, src_masks, None, src_boxes.float(),
+                           src_labels.to(torch.int64), canvas_hw, lazy_masks)
+
+
+def remove_background(image, masks, out=None):
+    """CopyPaste.remove_background (custom_copypaste.py:101-109; INPUT.RM_BG_PROB): image * any(masks, dim=0) in ONE
+    dgx_remove_background call on the current stream.  image uint8 (3,h,w), masks uint8 / bool (n,h,w) (any non-zero byte counts as
+    set; n == 0: an all-zero image) -- GPU tensors.  out: where the result goes, uint8 (3,h,w) contiguous; `out is image` works in
+    place; None allocates.  Returns out."""
+    if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[0] != 3:
+        raise ValueError("remove_background: image must be uint8 (3, h, w), got %s %s" % (image.dtype, tuple(image.shape)))
+    if masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    if masks.dtype != torch.uint8 or masks.dim() != 3 or tuple(masks.shape[1:]) != tuple(image.shape[1:]):
+        raise ValueError("remove_background: masks %s %s do not match the image %s" % (masks.dtype, tuple(masks.shape), tuple(image.shape)))
+    if out is None:
+        image = image.contiguous()
+        out = torch.empty_like(image)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != tuple(image.shape) or out.device != image.device:
+        raise ValueError("remove_background: out %s %s does not match the image %s" % (out.dtype, tuple(out.shape), tuple(image.shape)))
+    n, h, w = int(masks.shape[0]), int(image.shape[1]), int(image.shape[2])
+    masks = masks.contiguous()
+    L.check(L.lib().dgx_remove_background(L.ptr(image), L.ptr(masks) if n else None, n, h, w, L.ptr(out), L.stream()), "dgx_remove_background")
+    return out
 
 
 def self_copy_merge(sources):

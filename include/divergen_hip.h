@@ -442,6 +442,27 @@ int dgx_self_copy_paste_merged(const uint8_t* dst_image, const uint8_t* dst_mask
                                const int32_t* sel, int m, int H, int W, uint8_t* out_image, uint8_t* out_masks,
                                float* out_boxes, uint8_t* out_valid, int32_t* workspace, void* stream);
 
+/* dgx_self_copy_paste for a source that is pasted whole (CopyPaste(selected=False): INPUT.SCP_SRC_OBJ_SELECT False, INPUT.SCP_TYPE
+ * 'in_domain' / 'cas'; DG/divergen/data/custom_build_copypaste_mapper.py:764-765, transforms/custom_copypaste.py:282-283): the same
+ * step with sel = 0 .. ns - 1 and m = ns, without a sel array and without the bound of 99 (that bound is _select_object's; an LVIS
+ * image can bring several hundred objects).  out_masks u8 (n0+ns,H,W); workspace as for dgx_self_copy_paste.  ns == 0 is legal
+ * (nothing is pasted).  Errors as dgx_self_copy_paste; ceil(ns / 99) > 65535 source plane groups, n0 + ns >= 2^31 or
+ * (n0 + ns) * H * W beyond 64 bits -> DGX_ERR_UNSUPPORTED. */
+int dgx_self_copy_paste_all(const uint8_t* dst_image, const uint8_t* dst_masks, const float* dst_boxes0, int n0, int h1, int w1,
+                            const uint8_t* src_image, const uint8_t* src_masks, int ns, int hs, int ws, int H, int W,
+                            uint8_t* out_image, uint8_t* out_masks, float* out_boxes, uint8_t* out_valid, int32_t* workspace,
+                            void* stream);
+
+/* Background removal (INPUT.RM_BG_PROB; CopyPaste.remove_background, DG/divergen/data/transforms/custom_copypaste.py:101-109):
+ * out = any_n(masks) ? image : 0 per pixel, all three channels.
+ *   image, out_image u8 (3,h,w); masks u8 (n,h,w), any non-zero byte counts as set.  out_image == image (in place) is allowed: a lane
+ *   reads its 16 pixels before it writes them.  n == 0 is legal (masks may be NULL) and writes an all-zero image, as torch.any over an
+ *   empty stack gives.  The image is read only where the union has a pixel.  Sizes need not be multiples of 16 and the bases need not
+ *   be aligned (byte accesses then).
+ * Errors: NULL image / out_image, h or w <= 0, n < 0, n > 0 with NULL masks -> DGX_ERR_BAD_ARG; h * w >= 2^31 -> DGX_ERR_UNSUPPORTED;
+ * nothing launched in either case. */
+int dgx_remove_background(const uint8_t* image, const uint8_t* masks, int n, int h, int w, uint8_t* out_image, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Fused parameter update over a flat arena: per-element gradient value clip, AdamW, EMA lerp of
  * the PRE-step weights (the reference updates the EMA before optimizer.step: DG/train_net.py:262-284),
