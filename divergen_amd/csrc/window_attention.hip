@@ -8,6 +8,14 @@
 // Backward: a wave owns a 16-KEY strip (dK, dV and the rel-pos-bias gradient are wave-local and
 // the bias gradient accumulates in registers across the windows of a chunk); dS goes through LDS
 // once for dQ = dS K.
+//
+// Rounding contract (tests/_attn_ref64.py states it as an emulation and as per-element bounds): bf16 inputs and outputs; logits,
+// softmax statistics and every accumulation fp32; P (forward: exp2(s - max), normalised behind the MFMA; backward: exp2(s - lse))
+// and dS rounded to bf16 where they feed an MFMA; one final bf16 rounding of out / dq / dk / dv; lse and the bias-table gradient
+// fp32, the latter summed from the UNROUNDED dS.  The backward's `out` is an INPUT: delta = rowsum(dO * out) is formed from the bf16
+// tensor it is handed (the forward's result), and dq / dk / the table gradient are those of that delta -- the tests' float64
+// reference is handed the same tensor.  (At a peaked softmax row, dS is nothing but P times the 2^-8 rounding of out inside delta.)
+// The shift mask is the reference's additive -100 in BOTH directions, never an exclusion of the masked keys.
 #include "dgx_common.h"
 #include <type_traits>
 #include <map>
@@ -615,8 +623,10 @@ __global__ __launch_bounds__((WinCfg<WS>::NT + (HELP ? 3 : 0)) * 64) void win_at
         // Shifted windows: most windows of a shifted layer lie inside ONE region (25 of the 36 of a 6 x 6 grid) and need no mask; the
         // phase is VALU-bound with three waves per SIMD, so the 16 instructions per query tile that fetch, spread and compare the region
         // ids cost it 60 % (6 900 against 4 200 cycles per window on the harness).  Such a window skips them;
-        // in the others a masked pair's probability is SET to zero behind the exponential (the reference's exp(s - 100 - lse) is below
-        // 4e-44 times the unmasked value: zero in the bf16 operands it feeds, and nothing in an fp32 sum next to real terms).
+        // in the others a masked pair gets the reference's ADDITIVE -100 in front of the exponential, exactly as in the forward kernel --
+        // not p = 0: where a query's own region scores 100 or more below a key outside it, the masked key still carries the row
+        // (lse says so), and a backward that drops it returns the gradient of another function
+        // (tests/test_gpu_attention_numerics.py, mask semantics).
         bool mixed = false;
         if (MASKED) {
             const int r0 = reg_s[0];
@@ -660,8 +670,8 @@ __global__ __launch_bounds__((WinCfg<WS>::NT + (HELP ? 3 : 0)) * 64) void win_at
                     for (int r = 0; r < 4; ++r) {
                         float sv = __builtin_fmaf(s[r], scale2, PK ? bv[r] : tbl_k[ov[r]]);       // log2 domain (bias row, lse pre-scaled)
                         if (N % 16 != 0) sv += kneg;
+                        if (MK) sv += rv[r] != rk ? -100.0f * DGX_LOG2E : 0.0f;
                         pv[r] = __builtin_amdgcn_exp2f(sv);
-                        if (MK) pv[r] = rv[r] != rk ? 0.0f : pv[r];
                         dsv[r] = pv[r] * dp[r];
                         dbias[qt < NT ? qt : 0][r] += dsv[r];
                     }

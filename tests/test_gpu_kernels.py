@@ -28,17 +28,17 @@ def bf(x):
 
 
 # ------------------------------------------------------------------ window attention
-def _attn_ref(qkv, table, region, nH, ws, scale):
-    """fp32 oracle math on the bf16-rounded inputs (same contract as the kernel)."""
+def _attn_ref(qkv, table, region, nH, ws, scale, dtype=torch.float32):
+    """fp32 oracle math on the bf16-rounded inputs (same contract as the kernel); dtype=torch.float64: the same in double."""
     B_, N, _ = qkv.shape
-    q, k, v = qkv.float().reshape(B_, N, 3, nH, 32).permute(2, 0, 3, 1, 4)
+    q, k, v = qkv.to(dtype).reshape(B_, N, 3, nH, 32).permute(2, 0, 3, 1, 4)
     s = (q * scale) @ k.transpose(-2, -1)
     idx = OSW.relative_position_index(ws)
     s = s + table[idx.reshape(-1)].reshape(N, N, nH).permute(2, 0, 1)[None]
     if region is not None:
         nW = region.shape[0]
-        r = region.float()
-        m = (r[:, None, :] != r[:, :, None]).float() * -100.0
+        r = region.to(dtype)
+        m = (r[:, None, :] != r[:, :, None]).to(dtype) * -100.0
         s = (s.reshape(B_ // nW, nW, nH, N, N) + m[None, :, None]).reshape(B_, nH, N, N)
     a = torch.softmax(s, -1)
     return (a @ v).transpose(1, 2).reshape(B_, N, nH * 32)
