@@ -162,7 +162,7 @@ def get_cfg():
     #   (divergen_amd/csrc/poisson_blend.hip); without the key 'possion' is refused at start-up.
     cfg.INPUT.CP_POISSON = False
     #   INPUT.SCP_MULTI_SRC: admits INPUT.SCP_NUM_SRC 2 .. 4 to the self-copy methods of INPUT.USE_COPY_METHOD: the sources are merged
-    #   on the device first (divergen_amd/csrc/self_copy_merge.hip), which costs one more read-back of validity bytes and boxes per
+    #   on the device first (dgx_self_copy_merge, divergen_amd/csrc/self_copy.hip), which costs one more read-back of validity bytes and boxes per
     #   sample; without the key SCP_NUM_SRC != 1 is refused at start-up.
     cfg.INPUT.SCP_MULTI_SRC = False
     #   INPUT.SCP_SRC_MODES: admits, to the self-copy methods of INPUT.USE_COPY_METHOD, INPUT.SCP_TYPE 'in_domain' / 'cas' / 'the_cls' /

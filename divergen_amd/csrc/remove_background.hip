@@ -38,17 +38,14 @@ __global__ __launch_bounds__(256) void rb_kernel(const uint8_t* image, const uin
 extern "C" int dgx_remove_background(const uint8_t* image, const uint8_t* masks, int n, int h, int w, uint8_t* out_image, void* stream) {
     if (!image || !out_image || h <= 0 || w <= 0 || n < 0 || (n > 0 && !masks)) return DGX_ERR_BAD_ARG;
     if ((int64_t)h * w >= ((int64_t)1 << 31)) return DGX_ERR_UNSUPPORTED;
-    auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     const bool wide = (w % SCX) == 0;
     RbFlags fl;
-    fl.img_vec = wide && al(image);
-    fl.mask_vec = wide && al(masks);
-    fl.out_vec = wide && al(out_image);
+    fl.img_vec = wide && sc_aligned16(image);
+    fl.mask_vec = wide && sc_aligned16(masks);
+    fl.out_vec = wide && sc_aligned16(out_image);
     const int ncx = (w + SCX - 1) / SCX;
     const int64_t nchunk = (int64_t)h * ncx;
-    // one lane per 16 pixels
-    const int gx = (int)((nchunk + 255) / 256 < 2048 ? (nchunk + 255) / 256 : 2048);
-    hipLaunchKernelGGL(rb_kernel, dim3(gx), dim3(256), 0, (hipStream_t)stream, image, masks, n, h, w, ncx, fl, out_image);
+    hipLaunchKernelGGL(rb_kernel, dim3(ScGrid(nchunk).gx), dim3(256), 0, (hipStream_t)stream, image, masks, n, h, w, ncx, fl, out_image);
     DGX_LAUNCH_CHECK();
     return DGX_OK;
 }

@@ -1,5 +1,6 @@
-// What the self copy-paste kernels share (self_copy.hip: one paste step; self_copy_merge.hip: several sources folded first):
-// 16 pixels per lane, the vector-or-byte row accesses, the per-object statistics (count, x_min, x_max, y_min, y_max) of a plane.
+// What the self copy-paste kernels (self_copy.hip: one paste step, and several sources folded first) and the background removal
+// (remove_background.hip) share: 16 pixels per lane, the vector-or-byte row accesses, the per-object statistics (count, x_min, x_max,
+// y_min, y_max) of a plane, the launch geometry on the host.
 #pragma once
 #include "dgx_common.h"
 
@@ -90,3 +91,23 @@ __device__ __forceinline__ bool sc_resolve(const int32_t* s, const float* old, f
     for (int i = 0; i < 4; ++i) box_ok = box_ok && fabsf(b[i] - old[i]) <= 10.0f;
     return box_ok || s[0] > 300;
 }
+
+// ---- host side
+static inline bool sc_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static inline int64_t sc_pad4(int64_t n) { return (n + 3) & ~(int64_t)3; }
+// workgroups of 256 lanes over n items, grid-stride beyond 2048
+static inline int sc_blocks(int64_t n) { return (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048); }
+
+// Launch geometry over nchunk 16-pixel chunks, one lane each: gx workgroups; a kernel that loops over planes splits them into `want`
+// groups over grid.y so that small frames still fill the chip.
+struct ScGrid {
+    int gx, want;
+    explicit ScGrid(int64_t nchunk) : gx(sc_blocks(nchunk)), want(gx >= 1024 ? 1 : (1024 + gx - 1) / gx) {}
+    // n planes, at most cap per group (what the kernel's LDS holds): the grid, the planes per group in `per`.  n == 0: one empty group.
+    dim3 split(int n, int cap, int& per) const {
+        const int groups = want < n ? want : (n > 0 ? n : 1);
+        per = n > 0 ? (n + groups - 1) / groups : 1;
+        if (per > cap) per = cap;
+        return dim3(gx, n > 0 ? (n + per - 1) / per : 1);
+    }
+};

@@ -823,15 +823,11 @@ _BLOB_FIELDS = (("image", lambda d: d["image"]), ("gt_masks", lambda d: d["insta
                 ("flat", lambda d: d["paste_pack"]["flat"]), ("desc", lambda d: d["paste_pack"]["desc"]), ("labels", lambda d: d["paste_pack"]["labels"]))
 
 
-# optional sections, present only in a sample that carries a self-copy source (CopyPasteMapper._call_self_copy)
-_BLOB_SCP_FIELDS = (("scp_image", lambda d: d["scp_src"]["image"]), ("scp_masks", lambda d: d["scp_src"]["masks"]),
-                    ("scp_boxes", lambda d: d["scp_src"]["boxes"]), ("scp_labels", lambda d: d["scp_src"]["labels"]))
-
-
-def _blob_scp_group_fields(i):
-    """The four sections of source group i of a sample whose scp_src is a LIST (INPUT.SCP_NUM_SRC > 1, two or more sources selected
-    something): scp<i>_image, scp<i>_masks, scp<i>_boxes, scp<i>_labels."""
-    return tuple(("scp%d_%s" % (i, k), lambda d, i=i, k=k: d["scp_src"][i][k]) for k in ("image", "masks", "boxes", "labels"))
+def _blob_scp_sections(prefix):
+    """The four optional sections of one self-copy source (CopyPasteMapper._call_self_copy) as (section name, key in the source's
+    dict): prefix "scp_" for the single source, "scp%d_" % i for group i of a sample whose scp_src is a LIST (INPUT.SCP_NUM_SRC > 1,
+    two or more sources selected something)."""
+    return tuple((prefix + k, k) for k in ("image", "masks", "boxes", "labels"))
 
 
 def pack_sample(d):
@@ -844,11 +840,13 @@ def pack_sample(d):
         return d
     fields = _BLOB_FIELDS if "paste_pack" in d else _BLOB_FIELDS[:4]
     multi = isinstance(d.get("scp_src"), list)
+    groups = []
     if multi:
-        for i in range(len(d["scp_src"])):
-            fields = fields + _blob_scp_group_fields(i)
+        groups = [("scp%d_" % i, g) for i, g in enumerate(d["scp_src"])]
     elif "scp_src" in d:
-        fields = fields + _BLOB_SCP_FIELDS
+        groups = [("scp_", d["scp_src"])]
+    for prefix, g in groups:
+        fields = fields + tuple((name, lambda d, g=g, k=k: g[k]) for name, k in _blob_scp_sections(prefix))
     parts, layout, off = [], [], 0
     for name, get in fields:
         t = get(d).contiguous()
@@ -917,12 +915,11 @@ def unpack_sample(d, device, ring=None):
         if d.get("blob_desc") is not None:
             out["paste_pack"]["desc_host"] = d["blob_desc"]
     if "scp_image" in f:
-        out["scp_src"] = {"image": f["scp_image"], "masks": f["scp_masks"], "boxes": f["scp_boxes"], "labels": f["scp_labels"],
-                          "hw": tuple(d["blob_scp_hw"])}
+        out["scp_src"] = dict({k: f[name] for name, k in _blob_scp_sections("scp_")}, hw=tuple(d["blob_scp_hw"]))
         if d.get("blob_scp_all"):
             out["scp_src"]["all"] = True
     if d.get("blob_scp_n"):
-        out["scp_src"] = [{k: f["scp%d_%s" % (i, k)] for k in ("image", "masks", "boxes", "labels")} for i in range(d["blob_scp_n"])]
+        out["scp_src"] = [{k: f[name] for name, k in _blob_scp_sections("scp%d_" % i)} for i in range(d["blob_scp_n"])]
     return out
 
 

@@ -217,6 +217,8 @@ def poisson_blend(image, rgba, x0, y0, max_iter=-1):
 
 SELF_COPY_MAX = 99      # dgx_self_copy_paste: m <= 99 (the reference draws m < min(ns + 1, 100))
 SELF_COPY_MAX_SRC = 4   # dgx_self_copy_merge: S <= 4 source images (DGX_SELF_COPY_MAX_SRC): the bound of INPUT.SCP_NUM_SRC
+# self_copy_paste's entry of libdgx and the most source objects it takes, by `merged`
+_SELF_COPY_ENTRY = {False: ("dgx_self_copy_paste", SELF_COPY_MAX), True: ("dgx_self_copy_paste_merged", SELF_COPY_MAX * SELF_COPY_MAX_SRC)}
 
 
 def self_copy_canvas(dst_hw, sel_boxes):
@@ -225,6 +227,14 @@ def self_copy_canvas(dst_hw, sel_boxes):
     import math
     b = sel_boxes.cpu().numpy() if isinstance(sel_boxes, torch.Tensor) else np.asarray(sel_boxes)
     return max(int(dst_hw[0]), math.ceil(b[..., 3].max())), max(int(dst_hw[1]), math.ceil(b[..., 2].max()))
+
+
+def _nothing_pasted(image, masks, boxes, labels, lazy_masks):
+    """The result of a self copy that pastes no object: the inputs as they are, every row of `masks` kept."""
+    out = dict(image=image, masks=masks, boxes=boxes, labels=labels)
+    if lazy_masks:
+        out["keep"] = torch.arange(int(masks.shape[0]), dtype=torch.int64, device=image.device)
+    return out
 
 
 def self_copy_paste(image, masks, boxes, labels, src_image, src_masks, src_boxes, src_labels, sel, canvas_hw=None, lazy_masks=False,
@@ -240,20 +250,16 @@ def self_copy_paste(image, masks, boxes, labels, src_image, src_masks, src_boxes
     pasted, the inputs come back as they are (the reference keeps the destination's boxes then).
     lazy_masks: `masks` holds ALL n0 + m rows and `keep` (i64) the rows of the surviving objects, for BitMasks(masks, index=keep).
     merged: the source is the accumulator of self_copy_merge (dgx_self_copy_paste_merged: up to 99 objects per merged source)."""
-    dev = image.device
     sel = np.asarray(sel, dtype=np.int64).reshape(-1)
-    m, n0, ns = int(sel.shape[0]), int(masks.shape[0]), int(src_masks.shape[0])
-    entry, most = ("dgx_self_copy_paste_merged", SELF_COPY_MAX * SELF_COPY_MAX_SRC) if merged else ("dgx_self_copy_paste", SELF_COPY_MAX)
+    m, ns = int(sel.shape[0]), int(src_masks.shape[0])
+    entry, most = _SELF_COPY_ENTRY[bool(merged)]
     if m > most:
         raise ValueError("self_copy_paste: %d source objects selected, at most %d" % (m, most))
     if m and (int(sel.min()) < 0 or int(sel.max()) >= ns):
         raise ValueError("self_copy_paste: selected source index outside [0, %d): %s" % (ns, sel.tolist()))
     if m == 0:
-        out = dict(image=image, masks=masks, boxes=boxes, labels=labels)
-        if lazy_masks:
-            out["keep"] = torch.arange(n0, dtype=torch.int64, device=dev)
-        return out
-    sel_t = upload_i32(sel, dev)
+        return _nothing_pasted(image, masks, boxes, labels, lazy_masks)
+    sel_t = upload_i32(sel, image.device)
     sel_boxes = src_boxes.float().index_select(0, sel_t.long())
     sel_labels = src_labels.to(torch.int64).index_select(0, sel_t.long())
     return _self_copy_step(entry, image, masks, boxes, labels, src_image, src_masks, sel_t, sel_boxes, sel_labels, canvas_hw, lazy_masks)
@@ -293,15 +299,11 @@ def self_copy_paste_all(image, masks, boxes, labels, src_image, src_masks, src_b
     CopyPaste(selected=False) pastes (INPUT.SCP_SRC_OBJ_SELECT False, INPUT.SCP_TYPE 'in_domain' / 'cas'; mapper.py:764-765,
     custom_copypaste.py:282-283).  No `sel` and no bound of 99: that bound is _select_object's draw, a source pasted whole brings all its
     ns objects.  Arguments and the returned dict as self_copy_paste; ns == 0: nothing is pasted, the inputs come back as they are."""
-    dev = image.device
-    n0, ns = int(masks.shape[0]), int(src_masks.shape[0])
+    ns = int(src_masks.shape[0])
     if int(src_boxes.shape[0]) != ns or int(src_labels.shape[0]) != ns:
         raise ValueError("self_copy_paste_all: %d source masks, %d boxes, %d labels" % (ns, int(src_boxes.shape[0]), int(src_labels.shape[0])))
     if ns == 0:
-        out = dict(image=image, masks=masks, boxes=boxes, labels=labels)
-        if lazy_masks:
-            out["keep"] = torch.arange(n0, dtype=torch.int64, device=dev)
-        return out
+        return _nothing_pasted(image, masks, boxes, labels, lazy_masks)
     return _self_copy_step("dgx_self_copy_paste_all", image, masks, boxes, labels, src_image, src_masks, None, src_boxes.float(),
                            src_labels.to(torch.int64), canvas_hw, lazy_masks)
 

@@ -111,6 +111,40 @@ def test_kernels_equal_restatement_on_ragged_sizes(geom):
     _assert_paste_equal(out, ref, len(dst[1]))
 
 
+def _rect_source(rng, hw, rects, strays=()):
+    """one rectangle (y0, y1, x0, x1) per object, boxes of the rectangles alone; strays (object, y, x): an 8 x 8 block the box leaves out"""
+    masks = np.zeros((len(rects),) + hw, np.uint8)
+    for i, (y0, y1, x0, x1) in enumerate(rects):
+        masks[i, y0:y1, x0:x1] = 1
+    boxes = np.array([[x0, y0, x1, y1] for y0, y1, x0, x1 in rects], np.float32)
+    for i, y, x in strays:
+        masks[i, y:y + 8, x:x + 8] = 1
+    return rng.integers(0, 256, (3,) + hw, dtype=np.uint8), masks, boxes, rng.integers(0, 1203, len(rects)).astype(np.int64)
+
+
+def test_merge_where_the_frame_alone_fills_the_chip():
+    """Sources of 2048 x 2048: 2048 * 128 chunks are 1024 workgroups in x, so no kernel splits its planes over grid.y (one plane group),
+    and stage 2 runs in place at that geometry.  Source 0 brings A, B, C, source 1 D, E, source 2 F, G.  Stage 1, canvas (1715, 1715)
+    (no multiple of 16): D covers B whole (dropped); the blocks of A and D beyond the canvas are cut off.  Stage 2, in place, canvas
+    (1730, 1730): F covers E whole (dropped), G takes the left of C, whose box moves by 250 with 75000 pixels left (kept)."""
+    from divergen_amd.layers import self_copy_merge, self_copy_paste_multi
+    rng = np.random.default_rng(2048)
+    hw = (2048, 2048)
+    sources = [_rect_source(rng, hw, [(100, 400, 100, 500), (600, 900, 600, 1000), (1200, 1500, 200, 700)], strays=[(0, 1800, 1800)]),
+               _rect_source(rng, hw, [(550, 950, 550, 1050), (1700, 1715, 1700, 1715)], strays=[(0, 1900, 1900)]),
+               _rect_source(rng, hw, [(1690, 1730, 1690, 1730), (1150, 1550, 150, 450)])]
+    dst = _scene(rng, 6, 600, 800, big=True)
+    ref = MR.self_copy_multi(*dst, sources)
+    assert ref["merge"]["hw"] == [(1715, 1715), (1730, 1730)]
+    valid = ref["merge"]["valid"]
+    assert valid.tolist() == [True, False, True, True, False, True, True]      # B at stage 1, E at stage 2
+    assert not valid[:5].all() and valid[:5].any()             # an accumulator object dropped, another kept
+    acc = self_copy_merge([tuple(_gpu(*s)) for s in sources])
+    _assert_merge_equal(acc, ref["merge"])
+    out = self_copy_paste_multi(*_gpu(*dst), [tuple(_gpu(*s)) for s in sources], lazy_masks=True)
+    _assert_paste_equal(out, ref, len(dst[1]))
+
+
 def _grid_source(rng, h, w, cells, label0):
     """one 6 x 6 square per listed cell of the 8 x 8 grid of an (h, w) frame: objects that cannot cover each other"""
     per_row = w // 8
