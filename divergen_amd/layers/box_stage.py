@@ -94,6 +94,8 @@ def box_stage_supported(box_head, predictor):
     fcs = getattr(box_head, "fcs", None)
     if fcs is None or len(fcs) != 2 or not predictor.fused_supported or predictor.only_paste_sup:
         return False
+    if getattr(predictor, "use_zeroshot_cls", False):      # the open-vocabulary predictor is not one cls_score | bbox_pred GEMM
+        return False
     params = (fcs[0].weight, fcs[0].bias, fcs[1].weight, fcs[1].bias, predictor.cls_score.weight, predictor.cls_score.bias,
               predictor.bbox_pred.weight, predictor.bbox_pred.bias)
     return (arena_resident(params) and getattr(predictor.cls_score.weight, "_dgx16tg", None) is not None

@@ -347,3 +347,43 @@ def groupnorm_relu(x, weight, bias, num_groups, eps=1e-5, relu=True):
     with torch.autocast("cuda", enabled=False):
         y = _GroupNormReLU.apply(xp, weight, bias, num_groups, eps, relu)
     return y.permute(0, 3, 1, 2)
+
+
+class _L2NormalizeRows(torch.autograd.Function):
+    """t * F.normalize(x, p=2, dim=1, eps=1e-12) on libdgx (dgx_l2norm_rows_fwd / _bwd): x f32|bf16 (R, D) -> bf16 (R, D)."""
+
+    @staticmethod
+    def forward(ctx, x, t):
+        x = x.contiguous()
+        R, D = x.shape
+        y = torch.empty(R, D, dtype=torch.bfloat16, device=x.device)
+        rnorm = torch.empty(R, dtype=torch.float32, device=x.device)
+        L.check(L.lib().dgx_l2norm_rows_fwd(L.ptr(x), L.ptr(y), L.ptr(rnorm), R, D, float(t), L.dtype_code(x), L.stream()),
+                "dgx_l2norm_rows_fwd")
+        ctx.save_for_backward(x, rnorm)
+        ctx.t = float(t)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, rnorm = ctx.saved_tensors
+        R, D = x.shape
+        g = g.contiguous()
+        if g.dtype != torch.bfloat16:
+            g = g.to(torch.bfloat16)
+        dx = torch.empty(R, D, dtype=torch.bfloat16, device=x.device)
+        L.check(L.lib().dgx_l2norm_rows_bwd(L.ptr(g), L.ptr(x), L.ptr(rnorm), L.ptr(dx), R, D, ctx.t, L.dtype_code(x), L.stream()),
+                "dgx_l2norm_rows_bwd")
+        return (dx if x.dtype == torch.bfloat16 else dx.to(x.dtype)), None
+
+
+def l2_normalize_rows(x, temperature=1.0):
+    """x (R, D) f32|bf16 -> temperature * x / max(||x||_2, 1e-12) per row (zero_shot_classifier.py:47,78,83).  GPU tensors run
+    dgx_l2norm_rows_fwd/bwd and return bf16 (D % 8 == 0, 8 <= D <= 4096; anything else raises); host tensors take F.normalize
+    (host logic tests) and keep their dtype."""
+    if not x.is_cuda:
+        return temperature * torch.nn.functional.normalize(x, p=2, dim=1, eps=1e-12)
+    if x.dim() != 2 or x.shape[1] % 8 or not 8 <= x.shape[1] <= 4096:
+        raise L.DgxError("l2_normalize_rows: (R, D) rows with D %% 8 == 0 and 8 <= D <= 4096 required, got %s" % (tuple(x.shape),))
+    with torch.autocast("cuda", enabled=False):
+        return _L2NormalizeRows.apply(x, temperature)

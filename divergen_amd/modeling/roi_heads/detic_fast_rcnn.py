@@ -1,7 +1,8 @@
 """DeticFastRCNNOutputLayers: cls_score / bbox_pred + sigmoid-CE with federated loss + L1 box loss.
 Mirrors DG/divergen/modeling/roi_heads/detic_fast_rcnn.py:31-466 and
 D2/modeling/roi_heads/fast_rcnn.py:45-460 for the configuration the shipped YAMLs select
-(USE_SIGMOID_CE, USE_FED_LOSS, CLS_AGNOSTIC_BBOX_REG, smooth_l1 beta 0, no zero-shot classifier)."""
+(USE_SIGMOID_CE, USE_FED_LOSS, CLS_AGNOSTIC_BBOX_REG, smooth_l1 beta 0), plus the open-vocabulary predictor of
+USE_ZEROSHOT_CLS (:106-118: cls_score = ZeroShotClassifier, bbox_pred = Linear-ReLU-Linear)."""
 import json
 import math
 
@@ -14,7 +15,9 @@ from ...layers import batched_nms
 from ...layers.linear_ops import Linear, group_parameters, linear_padded
 from ...structures import Boxes, Instances
 from ...utils.events import get_event_storage
+from ..backbone.fpn import c2_xavier_fill
 from ..box_regression import Box2BoxTransform
+from .zero_shot_classifier import ZeroShotClassifier
 
 
 import os
@@ -163,22 +166,35 @@ class DeticFastRCNNOutputLayers(nn.Module):
                  test_topk_per_image=100, cls_agnostic_bbox_reg=False, smooth_l1_beta=0.0, box_reg_loss_type="smooth_l1",
                  loss_weight=1.0, mult_proposal_score=False, use_sigmoid_ce=False, use_fed_loss=False,
                  ignore_zero_cats=False, fed_loss_num_cat=50, prior_prob=0.01, cat_freq_path="",
-                 fed_loss_freq_weight=0.5, use_zeroshot_cls=False, divergen_box_loss=True, only_paste_sup=False, **unused):
+                 fed_loss_freq_weight=0.5, use_zeroshot_cls=False, cls_score=None, divergen_box_loss=True, only_paste_sup=False,
+                 **unused):
         super().__init__()
-        if use_zeroshot_cls or box_reg_loss_type != "smooth_l1":
-            raise NotImplementedError("USE_ZEROSHOT_CLS / non-smooth_l1 box losses are outside the shipped configs")
-        self.num_classes = num_classes
+        if box_reg_loss_type != "smooth_l1":
+            raise NotImplementedError("MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE %r: only 'smooth_l1' is built (the shipped configs)"
+                                      % (box_reg_loss_type,))
+        self.num_classes, self.use_zeroshot_cls = num_classes, use_zeroshot_cls
         input_size = input_shape.channels * (input_shape.width or 1) * (input_shape.height or 1)
-        self.cls_score = Linear(input_size, num_classes + 1)
-        self.bbox_pred = Linear(input_size, (1 if cls_agnostic_bbox_reg else num_classes) * 4)
-        # cls_score and bbox_pred read the same features: their rows sit back to back in the parameter arena (1454 + 4 -> 1464
-        # rows), one GEMM each way serves both (forward, input gradient, weight gradient)
-        group_parameters(self.cls_score.weight, self.bbox_pred.weight)
-        group_parameters(self.cls_score.bias, self.bbox_pred.bias)
-        nn.init.normal_(self.cls_score.weight, std=0.01)
-        nn.init.normal_(self.bbox_pred.weight, std=0.001)
-        for l in (self.cls_score, self.bbox_pred):
-            nn.init.constant_(l.bias, 0)
+        if use_zeroshot_cls:
+            # DG detic_fast_rcnn.py:106-118: the open-vocabulary classifier and a two-layer class-agnostic box regressor.  No arena
+            # group: the two read the same features through different first layers, so each Linear is its own GEMM
+            if cls_score is None:
+                raise ValueError("use_zeroshot_cls needs cls_score (a ZeroShotClassifier)")
+            self.cls_score = cls_score
+            self.bbox_pred = nn.Sequential(Linear(input_size, input_size), nn.ReLU(), Linear(input_size, 4))
+            c2_xavier_fill(self.bbox_pred[0])
+            nn.init.normal_(self.bbox_pred[-1].weight, std=0.001)
+            nn.init.constant_(self.bbox_pred[-1].bias, 0)
+        else:
+            self.cls_score = Linear(input_size, num_classes + 1)
+            self.bbox_pred = Linear(input_size, (1 if cls_agnostic_bbox_reg else num_classes) * 4)
+            # cls_score and bbox_pred read the same features: their rows sit back to back in the parameter arena (1454 + 4 -> 1464
+            # rows), one GEMM each way serves both (forward, input gradient, weight gradient)
+            group_parameters(self.cls_score.weight, self.bbox_pred.weight)
+            group_parameters(self.cls_score.bias, self.bbox_pred.bias)
+            nn.init.normal_(self.cls_score.weight, std=0.01)
+            nn.init.normal_(self.bbox_pred.weight, std=0.001)
+            for l in (self.cls_score, self.bbox_pred):
+                nn.init.constant_(l.bias, 0)
         self.box2box_transform, self.smooth_l1_beta = box2box_transform, smooth_l1_beta
         self.test_score_thresh, self.test_nms_thresh, self.test_topk_per_image = test_score_thresh, test_nms_thresh, test_topk_per_image
         self.mult_proposal_score, self.use_sigmoid_ce, self.use_fed_loss = mult_proposal_score, use_sigmoid_ce, use_fed_loss
@@ -186,7 +202,7 @@ class DeticFastRCNNOutputLayers(nn.Module):
         # BSGAL (BS/bsgal/modeling/roi_heads/detic_fast_rcnn.py:222-247): also report the classification loss of the rows matched
         # to pasted / to original instances (`loss_paste_ins`, `loss_nopaste_ins`), the terms its gradient comparison differentiates
         self.only_paste_sup = only_paste_sup
-        if use_sigmoid_ce:
+        if use_sigmoid_ce and not use_zeroshot_cls:      # (the open-vocabulary classifier's prior is its own cls_bias: USE_BIAS)
             nn.init.constant_(self.cls_score.bias, -math.log((1 - prior_prob) / prior_prob))
         if use_fed_loss or ignore_zero_cats:
             fw = load_class_freq(cat_freq_path, fed_loss_freq_weight)
@@ -199,7 +215,13 @@ class DeticFastRCNNOutputLayers(nn.Module):
     @classmethod
     def from_config(cls, cfg, input_shape, box2box_transform=None):
         h = cfg.MODEL.ROI_BOX_HEAD
-        return dict(input_shape=input_shape,
+        if h.USE_ZEROSHOT_CLS:
+            for key, on in (("MODEL.ROI_BOX_HEAD.WITH_SOFTMAX_PROP", h.WITH_SOFTMAX_PROP), ("MODEL.DYNAMIC_CLASSIFIER", cfg.MODEL.DYNAMIC_CLASSIFIER),
+                            ("MODEL.WITH_CAPTION", cfg.MODEL.WITH_CAPTION)):
+                if on:
+                    raise NotImplementedError("%s is not built: the open-vocabulary classifier trains on box annotations only "
+                                              "(no proposal-score branch, dynamic classifier, caption or image-label losses)" % key)
+        return dict(input_shape=input_shape, cls_score=ZeroShotClassifier(cfg, input_shape) if h.USE_ZEROSHOT_CLS else None,
                     box2box_transform=box2box_transform or Box2BoxTransform(weights=h.BBOX_REG_WEIGHTS),
                     num_classes=cfg.MODEL.ROI_HEADS.NUM_CLASSES, cls_agnostic_bbox_reg=h.CLS_AGNOSTIC_BBOX_REG,
                     smooth_l1_beta=h.SMOOTH_L1_BETA, test_score_thresh=cfg.MODEL.ROI_HEADS.SCORE_THRESH_TEST,
@@ -214,6 +236,13 @@ class DeticFastRCNNOutputLayers(nn.Module):
     def forward(self, x, classifier_info=(None, None, None)):
         if x.dim() > 2:
             x = torch.flatten(x, start_dim=1)
+        if classifier_info[2] is not None:
+            raise NotImplementedError("caption scores (classifier_info[2], MODEL.WITH_CAPTION) are not built: the box predictor "
+                                      "trains on box annotations only")
+        if self.use_zeroshot_cls:
+            return self.cls_score(x, classifier=classifier_info[0]), self._bbox_pred_rows(x)
+        if classifier_info[0] is not None:
+            raise NotImplementedError("a per-call vocabulary (classifier_info[0]) needs MODEL.ROI_BOX_HEAD.USE_ZEROSHOT_CLS")
         y = self.forward_joint(x)
         if y is not None:
             c1, nb = self.cls_score.out_features, self.bbox_pred.out_features
@@ -223,15 +252,30 @@ class DeticFastRCNNOutputLayers(nn.Module):
     def forward_joint(self, x):
         """(R, pad8(C + 1 + 4)) logits | box deltas | zero columns from ONE GEMM over the arena group, or None when the parameters
         are not arena resident (module used on its own)."""
+        if self.use_zeroshot_cls:       # no arena group: cls_score and bbox_pred are separate networks
+            return None
         w = self.cls_score.weight
         if getattr(w, "_dgx16g", None) is None:
             return None
         return linear_padded(x, w, self.cls_score.bias)
 
+    def _bbox_pred_rows(self, x):
+        """The open-vocabulary predictor's Linear-ReLU-Linear regressor; host tensors (logic tests) take torch's ops."""
+        if x.is_cuda:
+            return self.bbox_pred(x)
+        b = self.bbox_pred
+        return F.linear(F.relu(F.linear(x, b[0].weight, b[0].bias)), b[2].weight, b[2].bias)
+
+    @property
+    def num_box_deltas(self):
+        """Columns of bbox_pred's output (4 = class-agnostic)."""
+        last = self.bbox_pred[-1] if isinstance(self.bbox_pred, nn.Sequential) else self.bbox_pred
+        return last.out_features
+
     @property
     def fused_supported(self):
         """The one-pass loss / cascade kernels cover the shipped recipe: sigmoid CE, class-agnostic L1 box regression."""
-        return _FUSED_LOSSES and self.use_sigmoid_ce and self.bbox_pred.out_features == 4 and self.smooth_l1_beta < 1e-5
+        return _FUSED_LOSSES and self.use_sigmoid_ce and self.num_box_deltas == 4 and self.smooth_l1_beta < 1e-5
 
     def fused_ok(self, scores, deltas):
         return (_FUSED_LOSSES and scores.is_cuda and scores.shape[0] > 0 and self.use_sigmoid_ce and deltas.shape[1] == 4

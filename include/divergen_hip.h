@@ -584,6 +584,20 @@ int dgx_patch_merge_ln_bwd(const void* dy_bf16, const void* x, const float* mean
                            int W, int C0, int x_dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Row-wise L2 normalisation with a scale: y = t * F.normalize(x, p=2, dim=1, eps=1e-12), the arithmetic of Detic's open-vocabulary
+ * classifier (DG/divergen/modeling/roi_heads/zero_shot_classifier.py:47,78,83: the projected box features with t = NORM_TEMP, the
+ * class embeddings of a per-call vocabulary with t = 1).
+ *   x f32 or bf16 (x_dtype) (R,D);  y bf16 (R,D) = t * x / max(||x||_2, 1e-12);  rnorm f32 (R) = 1 / max(||x||_2, 1e-12), saved for
+ *   backward.  The sum of squares is taken in fp32; the row is read once.
+ * Backward: g bf16 (R,D), the saved x and rnorm -> dx bf16 (R,D) = t*rnorm*(g - xh*(xh.g)) with xh = x*rnorm; rows whose norm was
+ *   at or below the clamp (rnorm == 1e12) get dx = t*rnorm*g: the clamp is a constant there, as in torch's own backward.
+ * Constraints: D % 8 == 0 and 8 <= D <= 4096 (16-byte lanes, the row held in registers); anything else returns
+ *   DGX_ERR_UNSUPPORTED and launches nothing.  R == 0 is a no-op. */
+int dgx_l2norm_rows_fwd(const void* x, void* y_bf16, float* rnorm, int64_t R, int D, float t, int x_dtype, void* stream);
+int dgx_l2norm_rows_bwd(const void* g_bf16, const void* x, const float* rnorm, void* dx_bf16, int64_t R, int D, float t,
+                        int x_dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Residual + DropPath epilogue of a Swin block: out = x + scale[b] * y, y bf16 in token order (ws == 0)
  * or in window order (ws > 0: window_reverse + roll(+shift) + crop folded into the read).  Replaces
  * swintransformer.py:239-255 (window_reverse, roll, crop, drop_path, add).  x/out dtype f32|bf16;

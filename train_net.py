@@ -116,9 +116,13 @@ def _do_test(cfg, model):
     from collections import OrderedDict
     from divergen_amd.data.build import build_detection_test_loader
     from divergen_amd.evaluation import LVISEvaluator, inference_on_dataset, print_csv_format
+    from divergen_amd.modeling.utils import reset_cls_test, reset_cls_vocabularies
     results = OrderedDict()
     device = torch.device(cfg.MODEL.DEVICE)
-    for dataset_name in cfg.DATASETS.TEST:
+    vocab = reset_cls_vocabularies(cfg)            # MODEL.RESET_CLS_TESTS (DG/train_net.py:88-93): one classifier per test set
+    for d, dataset_name in enumerate(cfg.DATASETS.TEST):
+        if vocab is not None:
+            reset_cls_test(model, vocab[d][1], vocab[d][2])
         loader = build_detection_test_loader(cfg, dataset_name, device)
         out_dir = os.path.join(cfg.OUTPUT_DIR, "inference_{}".format(dataset_name))
         evaluator = LVISEvaluator(dataset_name, cfg, True, out_dir, max_dets_per_image=cfg.TEST.DETECTIONS_PER_IMAGE)
