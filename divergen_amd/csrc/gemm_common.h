@@ -1,10 +1,13 @@
 // Shared pieces of libdgx's forward / input-gradient GEMM kernels (gemm_nt.hip: 8 waves that load their own operands, two workgroups
-// per CU for the short contractions; gemm_lw.hip: 8 MFMA waves + 4 loader waves, persistent): problem descriptor, LDS-direct load
-// helper, exact-GELU arithmetic and the fused tails of the read-out (bias | bias + GELU with both tensors | x GELU'(f1) |
+// per CU for the short contractions; gemm_lw.hip: 8 MFMA waves + 4 loader waves, persistent; gemm_k192.hip: resident weight panel):
+// problem descriptor, LDS-direct load helper, the operand addressing and split-K pieces the tiled kernels share, exact-GELU arithmetic
+// and the fused tails of the read-out (bias | bias + GELU with both tensors | x GELU'(f1) |
 // x ReLU'(act) | window-reverse + DropPath + residual).
 #pragma once
 #include "dgx_common.h"
+#include "gemm_plan.h"
 #include "winmap.h"
+#include <type_traits>
 
 constexpr int GBK = 64;                 // K-step (elements): 128-byte tile rows
 static constexpr uint32_t G_OOB = 0x80000000u; // voffset beyond num_records: the lane's 16 bytes land in LDS as zeros
@@ -67,6 +70,72 @@ __device__ __forceinline__ void g_bar() {
     __builtin_amdgcn_sched_barrier(0);
 }
 
+// The tail compiled into an instantiation: MC >= 0 fixes the mode (3 / 6: mode 3 with a bf16 / fp32 residual stream), MC < 0 leaves it
+// a run-time field.  With the mode a run-time field the tail's operand prefetch sat under mode branches, and the compiler's wait-count
+// model, merging the path without a prefetch, waited for every outstanding load (vmcnt(0)) before the staging pass the prefetch was
+// meant to overlap (round 5, tools/isa_wait_scan.py).
+template <int MC> __device__ __forceinline__ void g_fix_mode(GemmP& P) {
+    if constexpr (MC == 6) { P.mode = 3; P.res_dtype = DGX_F32; }
+    else if constexpr (MC == 3) { P.mode = 3; P.res_dtype = DGX_BF16; }
+    else if constexpr (MC >= 0) P.mode = MC;
+}
+// Host side of the same: calls f(std::integral_constant<int, mc>) for a tail mc = dgxplan::tail_mc (the mode, 6 for an fp32 residual
+// stream; anything else arrives as 0).  Each launcher maps the values it has no instantiation for onto the one that serves them.
+template <class F> int g_with_mc(int mc, F&& f) {
+    switch (mc) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        default: return f(std::integral_constant<int, 0>{});
+    }
+}
+inline int g_tail_mc(const GemmP& P) { return dgxplan::tail_mc(P.mode, P.res_dtype == DGX_BF16); }
+
+// Grouped convolution: the record of the image that tile L belongs to (the last one with tile0 <= L); the caller patches A / C / M and
+// the image geometry of its own copy of the descriptor from it and goes on with tile L - tile0 of that image.  L comes out of a division,
+// which runs on the vector unit: pass it through readfirstlane first, which tells the compiler the value is uniform.  Constant indices
+// only: a dynamic index into the by-value descriptor would go through private memory and lose uniformity.
+__device__ __forceinline__ dgxgemm::GemmP::Grp g_group_of_tile(const GemmP& P, int L) {
+    dgxgemm::GemmP::Grp q = P.grp[0];
+#pragma unroll
+    for (int k = 1; k < dgxgemm::GEMM_MAXG; ++k)
+        if (k < P.ngrp && L >= P.grp[k].tile0) q = P.grp[k];
+    return q;
+}
+__device__ __forceinline__ void g_enter_group(GemmP& P, const dgxgemm::GemmP::Grp& q) {
+    P.A = q.A; P.C = q.C; P.M = q.M;
+    P.cmap_n = q.cn; P.cmap_h = q.ch; P.cmap_w = q.cw; P.conv_wp = q.wp;
+}
+// Byte offset of this lane's 16-byte chunk (logical chunk lc) of GEMM row m of the A operand, G_OOB for a row beyond M.  Implicit
+// convolution: row m is output pixel (n, y, x), which reads its position in the zero-bordered image.
+__device__ __forceinline__ uint32_t g_a_voff(const GemmP& P, int m, int lc) {
+    int64_t arow = m;
+    if (P.conv_kc) {
+        const int hw = P.cmap_h * P.cmap_w;
+        const int n = m / hw, r = m - n * hw;
+        const int y = r / P.cmap_w, x = r - y * P.cmap_w;
+        arow = ((int64_t)n * (P.cmap_h + 2) + y + 1) * P.conv_wp + x + 1;
+    }
+    return m < P.M ? (uint32_t)((arow * P.lda + lc * 8) * 2) : G_OOB;
+}
+// soffset of K-tile kta of the A operand; implicit convolution: tap shift (rows) + channel block of the tap
+__device__ __forceinline__ uint32_t g_a_soff(const GemmP& P, int kta) {
+    uint32_t s = (uint32_t)kta * (GBK * 2);
+    if (P.conv_kc) {
+        const int tap = kta / P.conv_kc, kc = kta - tap * P.conv_kc;
+        s = (uint32_t)((tap / 3) * P.conv_wp + tap % 3) * (uint32_t)(P.lda * 2) + (uint32_t)kc * (GBK * 2);
+    }
+    return s;
+}
+// bias entries of 4 consecutive columns (two packed bf16 pairs) as floats
+__device__ __forceinline__ void g_bias4(const u32x2 raw, float (&bv)[4]) {
+    bv[0] = __uint_as_float(raw[0] << 16); bv[1] = __uint_as_float(raw[0] & 0xffff0000u);
+    bv[2] = __uint_as_float(raw[1] << 16); bv[3] = __uint_as_float(raw[1] & 0xffff0000u);
+}
+
 constexpr float kGInvSqrt2 = 0.70710678118654752440f;
 constexpr float kGInvSqrt2Pi = 0.39894228040143267794f;
 __device__ __forceinline__ void g_unpack8(const u32x4 r, float (&v)[8]) {
@@ -96,6 +165,18 @@ __device__ __forceinline__ int64_t g_row_token(const GMap& m, int64_t orow, int&
     if (hh >= Hp) hh -= Hp;
     if (ww >= Wp) ww -= Wp;
     return (hh < m.H && ww < m.W) ? ((int64_t)b * m.H + hh) * m.W + ww : -1;
+}
+
+// Mode 3: (token << 32 | DropPath factor bits) of tile row `tid` (rows m0 ..) into the tile's LDS table, -1 for a padding row or one
+// beyond M.  The factor is fetched HERE, once per tile row -- as a load inside the read-out's `locate` it sat in front of every chunk's
+// store behind an s_waitcnt vmcnt(0) that also waited for the prefetched operands of the next slab and for the stores before it
+// (round 5, tools/isa_wait_scan.py).
+__device__ __forceinline__ void g_fill_rowtok(const GemmP& P, DGX_LDS int64_t* rowtok, int m0, int tid) {
+    int b = 0;
+    const int64_t orow = (int64_t)m0 + tid;
+    const int64_t tok = orow < P.M ? g_row_token(P.map, orow, b) : -1;
+    const float scv = (tok >= 0 && P.scale) ? P.scale[b] : 1.0f;
+    rowtok[tid] = tok < 0 ? -1 : ((tok << 32) | (int64_t)__float_as_uint(scv));
 }
 
 // Exact-GELU pieces  cdf(x) = (1 + erf(x / sqrt 2)) / 2  and  pdf(x) = exp(-x^2 / 2) / sqrt(2 pi)  from ONE exponential:
@@ -160,10 +241,8 @@ __device__ __forceinline__ float g_gelu_grad(float x) {
     return cdf + x * pdf;
 }
 
-// The fused tail of one 8-column chunk y = bf16(acc + bias) of output row gm (shared by the GEMM read-out and the split-K
-// fold).  tok / sc: mode 3 token index (>= 0) and DropPath factor of the row.
-// The fused tail of one 8-column chunk y = bf16(acc + bias) of output row gm, in two halves so that callers can put many
-// chunks' extra operands (saved pre-activation of mode 4, residual of mode 3) in flight before consuming any:
+// The fused tail of one 8-column chunk y = bf16(acc + bias) of output row gm (shared by the GEMM read-outs and the split-K
+// fold), in two halves so that callers can put many chunks' extra operands (saved pre-activation of mode 4, residual of mode 3) in flight before consuming any:
 // g_epi_prefetch issues the loads, g_epi_finish does the arithmetic and the stores.  tok / sc: mode 3 token index (>= 0)
 // and DropPath factor of the row.
 __device__ __forceinline__ void g_epi_prefetch(const GemmP& P, int gm, int gn, int64_t tok, u32x4& xa, u32x4& xb) {

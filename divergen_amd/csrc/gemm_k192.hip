@@ -29,9 +29,7 @@ __global__ __launch_bounds__(KwCfg<AR>::WAVES * 64, 1) void gemm_k192_kernel(KwP
     constexpr int KW_WAVES = KwCfg<AR>::WAVES, KW_AKT = KwCfg<AR>::AKT, KW_A_BYTES = KwCfg<AR>::A_BYTES, KW_AROWS = AR, RI = KwCfg<AR>::RI,
                   RQ = KwCfg<AR>::RQ;
     GemmP& P = K.g;
-    if constexpr (MC == 6) { P.mode = 3; P.res_dtype = DGX_F32; }
-    else if constexpr (MC == 3) { P.mode = 3; P.res_dtype = DGX_BF16; }
-    else P.mode = MC;
+    g_fix_mode<MC>(P);
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds_raw[];
     const int tid = threadIdx.x, l = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -153,9 +151,9 @@ __global__ __launch_bounds__(KwCfg<AR>::WAVES * 64, 1) void gemm_k192_kernel(KwP
                 for (int h = 0; h < 2; ++h) {
                     const int j = 2 * p + h;
                     const f32x4 a = acc[i][j];
-                    const float b0 = __uint_as_float(braw[j][0] << 16), b1 = __uint_as_float(braw[j][0] & 0xffff0000u);
-                    const float b2 = __uint_as_float(braw[j][1] << 16), b3 = __uint_as_float(braw[j][1] & 0xffff0000u);
-                    pk[h] = u32x2{pack_bf2(a[0] + b0, a[1] + b1), pack_bf2(a[2] + b2, a[3] + b3)};
+                    float bv[4];
+                    g_bias4(braw[j], bv);
+                    pk[h] = u32x2{pack_bf2(a[0] + bv[0], a[1] + bv[1]), pack_bf2(a[2] + bv[2], a[3] + bv[3])};
                 }
                 const u32x2 give = even ? pk[1] : pk[0];
                 const u32x2 got = u32x2{(uint32_t)__shfl_xor((int)give[0], 16), (uint32_t)__shfl_xor((int)give[1], 16)};
@@ -195,15 +193,14 @@ int launch_k192(KwParams& K, hipStream_t st, int grid) {
         once = true;
     }
     hipLaunchKernelGGL((gemm_k192_kernel<MC, AR>), dim3(grid), dim3(KwCfg<AR>::WAVES * 64), sm, st, K);
-    DGX_LAUNCH_CHECK();
     return DGX_OK;
 }
 }  // namespace
 
-// gemm_nt.hip's dispatch hands the K = 192 problems it takes here (bool: the shape and the tail are this kernel's)
+// gemm_nt.hip's launch path hands the problems that gemm_plan.h gives this kernel here (K = 192, N a multiple of 192, tails 0 .. 4).
+// The planner sees sizes only; what this kernel asks of the operands' addresses is answered here (GemmProblem::k192_operands).
 bool dgx_gemm_k192_takes(const GemmP& P) {
-    return P.K == 192 && P.lda >= 192 && P.N >= 192 && P.N % 192 == 0 && P.M >= 32768 && !P.conv_kc && P.ngrp == 0 && !P.relu && P.mode >= 0 &&
-           P.mode <= 4 && ((uintptr_t)P.A & 15) == 0 && ((uintptr_t)P.B & 15) == 0 && (P.lda & 7) == 0 && (P.ldb & 7) == 0;
+    return P.lda >= 192 && ((uintptr_t)P.A & 15) == 0 && ((uintptr_t)P.B & 15) == 0 && (P.lda & 7) == 0 && (P.ldb & 7) == 0;
 }
 int dgx_gemm_k192_launch(const GemmP& P0, hipStream_t st) {
     extern int dgx_get_reserved_cus(void);
@@ -212,13 +209,12 @@ int dgx_gemm_k192_launch(const GemmP& P0, hipStream_t st) {
     K.ntn = P0.N / KW_BROWS;
     K.row_tiles = 0;                               // (set per instantiation: rows per wave tile)
     K.wg_per_xcd = 32 - dgx_get_reserved_cus() / 8;
-    if (K.wg_per_xcd < K.ntn) return DGX_ERR_UNSUPPORTED;
+    if (P0.K != 192 || K.ntn < 1 || K.wg_per_xcd < K.ntn) return DGX_ERR_UNSUPPORTED;       // the planner never sends these
     const int grid = 8 * K.wg_per_xcd;
-    switch (P0.mode) {
-        case 0: case 1: return launch_k192<1, 32>(K, st, grid);
-        case 2: return launch_k192<2, 16>(K, st, grid);
-        case 3: return P0.res_dtype == DGX_BF16 ? launch_k192<3, 16>(K, st, grid) : launch_k192<6, 16>(K, st, grid);
-        case 4: return launch_k192<4, 16>(K, st, grid);
-        default: return DGX_ERR_UNSUPPORTED;
-    }
+    return g_with_mc(g_tail_mc(P0), [&](auto mc) {
+        constexpr int v = decltype(mc)::value;
+        if constexpr (v == 5) return (int)DGX_ERR_UNSUPPORTED;
+        else if constexpr (v <= 1) return launch_k192<1, 32>(K, st, grid);      // plain | bias: 32-row wave tiles
+        else return launch_k192<v, 16>(K, st, grid);
+    });
 }

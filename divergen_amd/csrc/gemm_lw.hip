@@ -87,9 +87,7 @@ template <int BM, int BN, int NSA, int NSB, int MC>
 __global__ __launch_bounds__(LW_THREADS) void gemm_lw_kernel(GemmP P0) {
     constexpr int EC = MC == 6 ? 2 : (MC == 3 || MC == 4 || MC == 5) ? 1 : 0;
     if constexpr (MC == 0) { if (P0.mode > 1) __builtin_unreachable(); }
-    else if constexpr (MC == 6) { P0.mode = 3; P0.res_dtype = DGX_F32; }
-    else if constexpr (MC == 3) { P0.mode = 3; P0.res_dtype = DGX_BF16; }
-    else P0.mode = MC;
+    else g_fix_mode<MC>(P0);
     using Cfg = LwCfg<BM, BN, NSA, NSB>;
     constexpr int WMF = Cfg::WMF, WNF = Cfg::WNF, NLA = Cfg::NLA, NLB = Cfg::NLB, SA = Cfg::SA, SBb = Cfg::SBb, B0 = Cfg::B0;
     constexpr int SROW = Cfg::SROW, STG0 = Cfg::STG0, CH = Cfg::CH, HC = Cfg::HC, NPASS = Cfg::NPASS, FPP = Cfg::FPP, HALF = Cfg::HALF;
@@ -115,12 +113,8 @@ __global__ __launch_bounds__(LW_THREADS) void gemm_lw_kernel(GemmP P0) {
         it.split = L0 - L * P0.splits;
         if (P0.ngrp > 0) {
             L = __builtin_amdgcn_readfirstlane(L);
-            dgxgemm::GemmP::Grp q = P0.grp[0];
-#pragma unroll
-            for (int k = 1; k < dgxgemm::GEMM_MAXG; ++k)
-                if (k < P0.ngrp && L >= P0.grp[k].tile0) q = P0.grp[k];
-            P.A = q.A; P.C = q.C; P.M = q.M;
-            P.cmap_n = q.cn; P.cmap_h = q.ch; P.cmap_w = q.cw; P.conv_wp = q.wp;
+            const dgxgemm::GemmP::Grp q = g_group_of_tile(P0, L);
+            g_enter_group(P, q);
             L -= q.tile0;
         }
         const int tm = L / P0.tiles_n, tn = L - tm * P0.tiles_n;
@@ -151,17 +145,7 @@ __global__ __launch_bounds__(LW_THREADS) void gemm_lw_kernel(GemmP P0) {
         auto setup = [&](int L0) {
             locate_item(L0, P, it);
 #pragma unroll
-            for (int s = 0; s < NLA; ++s) {
-                const int m = it.m0 + 8 * (lw + 4 * s) + rsub;
-                int64_t arow = m;
-                if (P.conv_kc) {                   // output pixel (n, y, x) -> its position in the zero-bordered image
-                    const int hw = P.cmap_h * P.cmap_w;
-                    const int n = m / hw, r = m - n * hw;
-                    const int y = r / P.cmap_w, x = r - y * P.cmap_w;
-                    arow = ((int64_t)n * (P.cmap_h + 2) + y + 1) * P.conv_wp + x + 1;
-                }
-                voffA[s] = m < P.M ? (uint32_t)((arow * P.lda + lc * 8) * 2) : G_OOB;
-            }
+            for (int s = 0; s < NLA; ++s) voffA[s] = g_a_voff(P, it.m0 + 8 * (lw + 4 * s) + rsub, lc);
 #pragma unroll
             for (int s = 0; s < NLB; ++s) {
                 const int n = it.n0 + 8 * (lw + 4 * s) + rsub;
@@ -173,11 +157,7 @@ __global__ __launch_bounds__(LW_THREADS) void gemm_lw_kernel(GemmP P0) {
         auto issue_a = [&](int t) {
             if (t >= it.NT) return;
             const int kta = it.kt0 + t;
-            uint32_t soffA = (uint32_t)kta * (GBK * 2);
-            if (P.conv_kc) {
-                const int tap = kta / P.conv_kc, kc = kta - tap * P.conv_kc;
-                soffA = (uint32_t)((tap / 3) * P.conv_wp + tap % 3) * (uint32_t)(P.lda * 2) + (uint32_t)kc * (GBK * 2);
-            }
+            const uint32_t soffA = g_a_soff(P, kta);
             const bool tail = (kta == NTK - 1) && (ktail != GBK) && !kt_ok;
             const uint32_t dst = ldsq + a_slot(t % NSA);
 #pragma unroll
@@ -335,16 +315,7 @@ __global__ __launch_bounds__(LW_THREADS) void gemm_lw_kernel(GemmP P0) {
         constexpr int NCH = CH * CPR;              // chunks per slab
         constexpr int ITERS = (NCH + LW_MFMA_THREADS - 1) / LW_MFMA_THREADS;
         if (P.mode == 3) {
-            if (tid < BM) {
-                int b = 0;
-                const int64_t orow = (int64_t)m0 + tid;
-                const int64_t tok = orow < P.M ? g_row_token(P.map, orow, b) : -1;
-                // (token, DropPath factor of its sample): the factor is fetched HERE, once per tile row -- as a load inside `locate` it sat in
-                // front of every chunk's store behind an s_waitcnt vmcnt(0) that also waited for the prefetched operands of the next slab and
-                // for the stores before it (round 5, tools/isa_wait_scan.py)
-                const float scv = (tok >= 0 && P.scale) ? P.scale[b] : 1.0f;
-                rowtok[tid] = tok < 0 ? -1 : ((tok << 32) | (int64_t)__float_as_uint(scv));
-            }
+            if (tid < BM) g_fill_rowtok(P, rowtok, m0, tid);
             lw_lgkm0();
             g_bar();
         }
@@ -508,13 +479,10 @@ int lw_launch_e(GemmP& P, hipStream_t st) {
 }
 template <int BM, int BN, int NSA, int NSB>
 int lw_launch_t(GemmP& P, hipStream_t st) {
-    switch (P.mode) {
-        case 2: return lw_launch_e<BM, BN, NSA, NSB, 2>(P, st);
-        case 3: return P.res_dtype == DGX_BF16 ? lw_launch_e<BM, BN, NSA, NSB, 3>(P, st) : lw_launch_e<BM, BN, NSA, NSB, 6>(P, st);
-        case 4: return lw_launch_e<BM, BN, NSA, NSB, 4>(P, st);
-        case 5: return lw_launch_e<BM, BN, NSA, NSB, 5>(P, st);
-        default: return lw_launch_e<BM, BN, NSA, NSB, 0>(P, st);
-    }
+    return g_with_mc(g_tail_mc(P), [&](auto mc) {
+        constexpr int v = decltype(mc)::value;
+        return lw_launch_e<BM, BN, NSA, NSB, (v <= 1 ? 0 : v)>(P, st);      // 0: plain | bias
+    });
 }
 }  // namespace
 

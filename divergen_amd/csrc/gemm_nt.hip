@@ -39,14 +39,10 @@ template <int BM, int BN, int NS_> struct GemmCfg {
 }  // namespace
 
 // MC >= 0: the fused tail is a compile-time constant (2: bias + GELU, 3 / 6: bf16 / fp32 residual, 4: x GELU'(f1)), as in gemm_lw --
-// the two-workgroup instantiation that runs the K <= 768 fused-tail GEMMs.  With the mode a run-time field the tail's operand prefetch
-// sat under mode branches, and the compiler's wait-count model, merging the path without a prefetch, waited for every outstanding load
-// (vmcnt(0)) before the staging pass the prefetch was meant to overlap (round 5, tools/isa_wait_scan.py).  MC = -1: run-time mode.
+// the two-workgroup instantiation that runs the K <= 768 fused-tail GEMMs (why: g_fix_mode).  MC = -1: run-time mode.
 template <int BM, int BN, int NS, int MINW, int MC = -1>
 __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
-    if constexpr (MC == 6) { P.mode = 3; P.res_dtype = DGX_F32; }
-    else if constexpr (MC == 3) { P.mode = 3; P.res_dtype = DGX_BF16; }
-    else if constexpr (MC >= 0) P.mode = MC;
+    g_fix_mode<MC>(P);
     using Cfg = GemmCfg<BM, BN, NS>;
     constexpr int NL = Cfg::NA + Cfg::NB;          // LDS-direct loads per wave per K-tile
     constexpr int WMF = Cfg::WMF, WNF = Cfg::WNF, NA = Cfg::NA, NB = Cfg::NB, SB = Cfg::SB, SROW = Cfg::SROW;
@@ -56,8 +52,9 @@ __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
     int L = L0 / P.splits;
     const int split = L0 - L * P.splits;           // the splits of a tile are neighbours on one XCD
     if (P.ngrp > 0) {                              // grouped convolution: this tile's image (P is this kernel's own copy of the descriptor)
-        L = __builtin_amdgcn_readfirstlane(L);    // (the division above runs on the vector unit: tell the compiler the value is uniform)
-        // constant indices only (a dynamic index into the by-value descriptor would go through private memory and lose uniformity)
+        // g_group_of_tile / g_enter_group of gemm_common.h written out: through the helpers the two-workgroup instantiations, which never
+        // run a grouped launch, come out with another register allocation (120 instead of 122 VGPRs)
+        L = __builtin_amdgcn_readfirstlane(L);
         dgxgemm::GemmP::Grp q = P.grp[0];
 #pragma unroll
         for (int k = 1; k < dgxgemm::GEMM_MAXG; ++k)
@@ -85,17 +82,7 @@ __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
     const int lc = (l & 7) ^ (((w & 1) << 2) | (rsub >> 1));
     uint32_t voffA[NA], voffB[NB];
 #pragma unroll
-    for (int s = 0; s < NA; ++s) {
-        const int m = m0 + 8 * (w + 8 * s) + rsub;
-        int64_t arow = m;
-        if (P.conv_kc) {                           // output pixel (n, y, x) -> its position in the zero-bordered image
-            const int hw = P.cmap_h * P.cmap_w;
-            const int n = m / hw, r = m - n * hw;
-            const int y = r / P.cmap_w, x = r - y * P.cmap_w;
-            arow = ((int64_t)n * (P.cmap_h + 2) + y + 1) * P.conv_wp + x + 1;
-        }
-        voffA[s] = m < P.M ? (uint32_t)((arow * P.lda + lc * 8) * 2) : G_OOB;
-    }
+    for (int s = 0; s < NA; ++s) voffA[s] = g_a_voff(P, m0 + 8 * (w + 8 * s) + rsub, lc);
 #pragma unroll
     for (int s = 0; s < NB; ++s) {
         const int n = n0 + 8 * (w + 8 * s) + rsub;
@@ -109,12 +96,7 @@ __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
     // one of the NL loads of a tile: k < NA -> A rows, else B rows
     auto issue_one = [&](int k, int t, int stage) {
         const int kta = kt0 + t;
-        const uint32_t soff = (uint32_t)kta * (GBK * 2);
-        uint32_t soffA = soff;
-        if (P.conv_kc) {                           // implicit convolution: tap shift (rows) + channel block of the tap
-            const int tap = kta / P.conv_kc, kc = kta - tap * P.conv_kc;
-            soffA = (uint32_t)((tap / 3) * P.conv_wp + tap % 3) * (uint32_t)(P.lda * 2) + (uint32_t)kc * (GBK * 2);
-        }
+        const uint32_t soff = (uint32_t)kta * (GBK * 2), soffA = g_a_soff(P, kta);
         const uint32_t dst = ldsw + (uint32_t)stage * SB;
         const bool tail = (kta == NTK - 1) && (ktail != GBK) && !kt_ok;
         if (k < NA) g_load_lds16(tail ? G_OOB : voffA[k], rA, dst + 8192u * k, soffA);
@@ -200,10 +182,8 @@ __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
     // Group 0 issues in its LOAD phase, group 1 right AFTER its MFMAs (both in I_{2t+3} for tile t + 2 when NS = 2).
     // Measured per K-tile of a 256x192 tile: loads of group 1 in front of its MFMAs 2525 cycles (their issue time delays the
     // whole interval), behind them 2106; both groups issuing in their LOAD phases (possible from 3 stages on) is no better.
-    constexpr bool G1_IN_LOAD = false;
-    if (grp == 0 || G1_IN_LOAD) {
+    if (grp == 0) {
         int is = NS - 1;                           // stage of the next tile to issue (tile t + NS - 1 at t >= 1)
-        if (grp == 1) g_bar();                     // #1: one phase behind group 0
         for (int t = 0; t < NT; ++t) {
             int ti = -1;
             if (t >= 1) {
@@ -213,13 +193,12 @@ __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
             load_phase(rs, ti, is);
             rs = rs + 1 == NS ? 0 : rs + 1;
             g_lgkm0();
-            if (grp == 1 && t + 1 < NT) wait_tile(t + 1);
-            g_bar();                               // group 0: #(2t+1), group 1: #(2t+2)
+            g_bar();                               // #(2t+1)
             mfmas();
-            if (grp == 0 && t + 1 < NT) wait_tile(t + 1);
-            g_bar();                               // group 0: #(2t+2), group 1: #(2t+3)
+            if (t + 1 < NT) wait_tile(t + 1);
+            g_bar();                               // #(2t+2)
         }
-        if (grp == 0) g_bar();                     // group 1's last phase
+        g_bar();                                   // group 1's last phase
     } else {
         int is = 0;                                // tile t + NS goes where tile t was
         g_bar();                                   // #1: one phase behind group 0
@@ -265,16 +244,7 @@ __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
     constexpr int CPR = BN / 8;                    // 16-byte chunks per tile row
     constexpr int ITERS = (BM * CPR + 511) / 512;
     if (P.mode == 3) {
-        if (tid < BM) {
-            int b = 0;
-            const int64_t orow = (int64_t)m0 + tid;
-            const int64_t tok = orow < P.M ? g_row_token(P.map, orow, b) : -1;
-            // (token, DropPath factor of its sample): the factor is fetched HERE, once per tile row -- as a load inside `locate` it sat in
-            // front of every chunk's store behind an s_waitcnt vmcnt(0) that also waited for the prefetched operands of the next slab and
-            // for the stores before it (round 5, tools/isa_wait_scan.py)
-            const float scv = (tok >= 0 && P.scale) ? P.scale[b] : 1.0f;
-            rowtok[tid] = tok < 0 ? -1 : ((tok << 32) | (int64_t)__float_as_uint(scv));
-        }
+        if (tid < BM) g_fill_rowtok(P, rowtok, m0, tid);
         __syncthreads();
     }
     // PFN chunks of the tail operands per lane are requested at a time: the whole tile for the one-workgroup-per-CU instantiations,
@@ -340,11 +310,7 @@ __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
         __builtin_amdgcn_sched_barrier(0);
         float bv[WNF][4];
 #pragma unroll
-        for (int j = 0; j < WNF; ++j) {
-            const uint32_t b01 = braw[j][0], b23 = braw[j][1];
-            bv[j][0] = __uint_as_float(b01 << 16); bv[j][1] = __uint_as_float(b01 & 0xffff0000u);
-            bv[j][2] = __uint_as_float(b23 << 16); bv[j][3] = __uint_as_float(b23 & 0xffff0000u);
-        }
+        for (int j = 0; j < WNF; ++j) g_bias4(braw[j], bv[j]);
 #pragma unroll
         for (int i = 0; i < WMF; ++i) {
             const int row = grp * (BM / 2) + 16 * i + c;
@@ -415,119 +381,77 @@ __global__ __launch_bounds__(256) void gemm_splitk_fold_kernel(GemmP P) {
     }
 }
 
+using dgxplan::GemmPlan;
+static_assert(dgxplan::BK == GBK && dgxplan::MAXG == dgxgemm::GEMM_MAXG, "gemm_plan.h restates these");
+
 namespace {
-struct TileChoice { int bm, bn; };
-int64_t g_ws_bytes_cur = 0;     // size of the workspace of the call being planned
-// Test / A-B knobs of the dispatch (dgx_dev_set): -1 / 0 = the library's own plan.  The product never sets them; the GEMM tests
-// force every tile shape and the split-K path through the one ABI entry with them, the tools compare own form A with own form B.
-struct DevKnobs { int lw = -1, two_wg = -1, tile_bm = 0, tile_bn = 0, splitk = 0, k192 = -1; } g_dev;
+dgxplan::DevKnobs g_dev;               // dgx_dev_set
 struct LastForm { int form = -1, bm = 0, bn = 0, splits = 0; } g_last;     // what the most recent dispatch launched (dgx_gemm_last_form)
+FILE* g_gemm_log = nullptr;            // one line per launch (dgx_dev_gemm_log), joined with a kernel trace by tools/gemm_insitu.py
 
-// split-K plan: few output tiles and a long contraction (box-head FC 1024 x 1024 x 12544, 3x3 convolutions over the small
-// FPN levels, stage-3 Linears) leave most CUs idle; S slabs of >= 4 K-tiles each fill them.  Returns 1 when not worth it.
-int choose_splits(int64_t tiles, int K, int64_t M, int64_t N, int64_t ws_bytes) {
-    const int nt = (K + GBK - 1) / GBK;
-    if (g_dev.splitk >= 1) {
-        const int v = g_dev.splitk;
-        return (v <= nt && (int64_t)v * M * N * 4 <= ws_bytes) ? v : 1;
-    }
-    if (tiles > 128 || nt < 8) return 1;
-    int S = (int)(256 / tiles);
-    if (S > nt / 4) S = nt / 4;
-    if (S > 16) S = 16;
-    while (S > 1 && (int64_t)S * M * N * 4 > ws_bytes) --S;
-    return S < 2 ? 1 : S;
-}
-
-// Tile selection: BN from the divisibility of N (every Swin width is a multiple of 192), BM from how well the tile count
-// fills whole rounds of 256 CUs (one workgroup per CU), weighted by the CU-side efficiency of the smaller tiles.
-static bool tile_192x256() { return true; }      // the 192 x 256 tile (2 stages) where it saves a round of the chip
-TileChoice choose_tile(int M, int N) {
-    if (g_dev.tile_bm) {
-        const int bm = g_dev.tile_bm, bn = g_dev.tile_bn;
-        if ((bm == 256 || bm == 192 || bm == 128) && (bn == 192 || bn == 128 || bn == 256) && !(bm == 256 && bn == 256) && !(bm == 192 && bn == 128))
-            return {bm, bn};
-    }
-    int bn;
-    if (N % 192 == 0) bn = 192;
-    else if (N % 256 == 0 || N > 1024) bn = 256;
-    else bn = 128;
-    const int cand[3] = {256, 192, 128};
-    const double eff[3] = {1.0, 0.97, 0.85};
-    double best = -1.0;
-    int bm = 128;
-    for (int i = 0; i < 3; ++i) {
-        const int b = cand[i];
-        if (bn == 256 && b == 256) continue;       // 256x256 does not fit two waves per SIMD (register file)
-        if (bn == 128 && b == 192) continue;       // 192-row tiles: instantiated for BN = 192 and 256
-        if (bn == 256 && b == 192 && !tile_192x256()) continue;
-        const int64_t tiles = (int64_t)((M + b - 1) / b) * ((N + bn - 1) / bn);
-        const int64_t rounds = (tiles + 255) / 256;
-        const double fill = (double)M * N / ((double)rounds * 256 * b * bn);
-        const double sc = fill * eff[i];
-        if (sc > best) { best = sc; bm = b; }
-    }
-    return {bm, bn};
-}
-
-template <int BM, int BN, int NS, int MINW = 2, int MC = -1>
-int launch_gemm(GemmP& P, hipStream_t st) {
+template <int BM, int BN, int NS, int MINW, int MC>
+int nt_launch_e(GemmP& P, hipStream_t st) {
     using Cfg = GemmCfg<BM, BN, NS>;
-    const int tiles_m = (P.M + BM - 1) / BM;
-    P.tiles_n = (P.N + BN - 1) / BN;
-    P.total = tiles_m * P.tiles_n;
-    const int nt = (P.K + GBK - 1) / GBK;
-    P.splits = choose_splits(P.total, P.K, P.M, P.N, P.ws ? g_ws_bytes_cur : 0);
-    P.kt_per_split = (nt + P.splits - 1) / P.splits;
-    P.splits = (nt + P.kt_per_split - 1) / P.kt_per_split;          // no empty split
-    P.per_xcd = (P.total * P.splits + 7) / 8;
     static bool once = false;
     if (!once) {
         if (hipFuncSetAttribute((const void*)gemm_nt_kernel<BM, BN, NS, MINW, MC>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS) != hipSuccess)
             return DGX_ERR_UNSUPPORTED;
         once = true;
     }
-    g_last = {MINW == 4 ? 2 : 0, BM, BN, P.splits};
     hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, NS, MINW, MC>), dim3(8 * P.per_xcd), dim3(512), Cfg::LDS, st, P);
-    if (P.splits > 1) {
-        const int64_t chunks = (int64_t)P.M * (P.N >> 3);
-        const int grid = (int)((chunks + 255) / 256 < 4096 ? (chunks + 255) / 256 : 4096);
-        hipLaunchKernelGGL(gemm_splitk_fold_kernel, dim3(grid), dim3(256), 0, st, P);
-    }
-    DGX_LAUNCH_CHECK();
     return DGX_OK;
+}
+// The gemm_nt instantiation of a plan: tile, stages and workgroups per CU (dgxplan::nt_stages), compiled-in tail.  Returns
+// DGX_ERR_UNSUPPORTED for one that is not instantiated.
+int gemm_nt_launch(GemmP& P, const GemmPlan& pl, hipStream_t st) {
+    const int bm = pl.bm, bn = pl.bn, ns = pl.stages;
+    if (pl.wg_per_cu == 2 && bm == 128 && bn == 192 && ns == 2)
+        return g_with_mc(pl.mc, [&](auto mc) {
+            constexpr int v = decltype(mc)::value;
+            return nt_launch_e<128, 192, 2, 4, (v == 2 || v == 3 || v == 4 || v == 6) ? v : -1>(P, st);
+        });
+    if (pl.wg_per_cu != 1) return DGX_ERR_UNSUPPORTED;
+    if (bm == 256 && bn == 192 && ns == 2) return nt_launch_e<256, 192, 2, 2, -1>(P, st);
+    if (bm == 192 && bn == 192 && ns == 3) return nt_launch_e<192, 192, 3, 2, -1>(P, st);
+    if (bm == 128 && bn == 192 && ns == 4) return nt_launch_e<128, 192, 4, 2, -1>(P, st);
+    if (bm == 192 && bn == 256 && ns == 2) return nt_launch_e<192, 256, 2, 2, -1>(P, st);
+    if (bm == 128 && bn == 256 && ns == 3) return nt_launch_e<128, 256, 3, 2, -1>(P, st);
+    if (bm == 256 && bn == 128 && ns == 3) return nt_launch_e<256, 128, 3, 2, -1>(P, st);
+    if (bm == 128 && bn == 128 && ns == 4) return nt_launch_e<128, 128, 4, 2, -1>(P, st);
+    return DGX_ERR_UNSUPPORTED;
 }
 }  // namespace
 
 int gemm_lw_launch(GemmP& P, int bm, int bn, hipStream_t st);     // gemm_lw.hip: the loader-wave form
-// Which form runs a problem (measured in situ, profiles/r04_gemm_insitu_*.txt): the loader-wave persistent kernel wins wherever the
-// read-out is plain (modes 0 / 1, the implicit convolutions: 0.65-0.97x the time, the skinny K = N = 192 projection excepted) and on
-// the long contractions (K > 768) with a residual or GELU tail; the two-workgroup form of gemm_nt keeps the K <= 768 GEMMs whose
-// tails read a cold operand or write two tensors (its second workgroup's main loop hides them).  dgx_dev_set("gemm_lw", 0 | 1) forces
-// gemm_nt | gemm_lw everywhere (tests and A/B tools only).
-static bool use_lw(const GemmP& P) {
-    if (g_dev.lw >= 0) return g_dev.lw == 1;
-    if (P.mode <= 1) return !(P.N <= 192 && P.K <= 192);
-    if (P.mode == 2 || P.mode == 3) return P.K > 768;
-    return false;
+bool dgx_gemm_k192_takes(const GemmP& P);                          // gemm_k192.hip: the HBM-bound K = 192 problems of Swin stage 0
+int dgx_gemm_k192_launch(const GemmP& P, hipStream_t st);
+
+// The plan of a filled descriptor (gemm_plan.h decides; nothing here does) and its line in the launch log
+static GemmPlan plan_and_log(const GemmP& P, int64_t ws_bytes) {
+    dgxplan::GemmProblem q;
+    q.M = P.M; q.N = P.N; q.K = P.K;
+    q.mode = P.mode; q.res_bf16 = P.res_dtype == DGX_BF16;
+    q.conv = P.conv_kc != 0; q.relu = P.relu != 0;
+    q.ngrp = P.ngrp;
+    int rows = P.ngrp ? 0 : P.M;                   // log: M = all images' rows
+    for (int i = 0; i < P.ngrp; ++i) { q.Ms[i] = P.grp[i].M; rows += P.grp[i].M; }
+    q.ws_bytes = P.ws ? ws_bytes : 0;
+    q.k192_operands = dgx_gemm_k192_takes(P);
+    const GemmPlan pl = dgxplan::plan_gemm(q, g_dev, dgx_get_reserved_cus() / 8);
+    if (g_gemm_log) { fprintf(g_gemm_log, "%d %d %d %d %d %d\n", rows, P.N, P.K, P.conv_kc ? 9 : P.mode, pl.bm, pl.bn); fflush(g_gemm_log); }
+    return pl;
 }
-// tiling fields of a bm x bn launch (what launch_gemm<> computes for its instantiation)
-static void plan_tiles(GemmP& P, int bm, int bn) {
-    const int tiles_m = (P.M + bm - 1) / bm;
-    P.tiles_n = (P.N + bn - 1) / bn;
-    P.total = tiles_m * P.tiles_n;
-    const int nt = (P.K + GBK - 1) / GBK;
-    P.splits = choose_splits(P.total, P.K, P.M, P.N, P.ws ? g_ws_bytes_cur : 0);
-    P.kt_per_split = (nt + P.splits - 1) / P.splits;
-    P.splits = (nt + P.kt_per_split - 1) / P.kt_per_split;
-    P.per_xcd = (P.total * P.splits + 7) / 8;
-}
-static int launch_lw(GemmP& P, int bm, int bn, hipStream_t st) {
-    plan_tiles(P, bm, bn);
-    const int rc = gemm_lw_launch(P, bm, bn, st);
+// Launch a planned problem: the plan's tiling into the descriptor, the form's kernel, the split-K fold behind it
+static int launch(GemmP& P, const GemmPlan& pl, hipStream_t st) {
+    P.tiles_n = pl.tiles_n; P.total = pl.total; P.per_xcd = pl.per_xcd;
+    P.splits = pl.splits; P.kt_per_split = pl.kt_per_split;
+    for (int i = 0; i < P.ngrp; ++i) P.grp[i].tile0 = pl.tile0[i];
+    const bool k192 = pl.form == dgxplan::FORM_K192;
+    const int rc = k192 ? dgx_gemm_k192_launch(P, st) : pl.form == dgxplan::FORM_LW ? gemm_lw_launch(P, pl.bm, pl.bn, st) : gemm_nt_launch(P, pl, st);
     if (rc != DGX_OK) return rc;
-    g_last = {1, bm, bn, P.splits};
-    if (P.splits > 1) {
+    if (k192) g_last = {pl.form, 32, 192, 1};
+    else g_last = {pl.form, pl.bm, pl.bn, pl.splits};
+    if (!k192 && pl.splits > 1) {
         const int64_t chunks = (int64_t)P.M * (P.N >> 3);
         const int grid = (int)((chunks + 255) / 256 < 4096 ? (chunks + 255) / 256 : 4096);
         hipLaunchKernelGGL(gemm_splitk_fold_kernel, dim3(grid), dim3(256), 0, st, P);
@@ -535,12 +459,7 @@ static int launch_lw(GemmP& P, int bm, int bn, hipStream_t st) {
     DGX_LAUNCH_CHECK();
     return DGX_OK;
 }
-static int dgx_gemm_dispatch(GemmP& P, hipStream_t st);
-static bool use_two_wg(const GemmP& P) {          // see dgx_gemm_dispatch
-    return g_dev.two_wg != 0 && P.N % 192 == 0 && P.K <= 768 && P.M >= (g_dev.two_wg >= 2 ? g_dev.two_wg : 4096) && !P.conv_kc;
-}
-static FILE* g_gemm_log = nullptr;     // one line per launch (dgx_dev_gemm_log), joined with a kernel trace by tools/gemm_insitu.py
-static FILE* gemm_log_file() { return g_gemm_log; }
+
 DGX_CLK_READER(dgx_dev_gemm_nt_clocks)
 extern "C" int dgx_dev_gemm_log(const char* path) {
     if (g_gemm_log) { fclose(g_gemm_log); g_gemm_log = nullptr; }
@@ -548,15 +467,15 @@ extern "C" int dgx_dev_gemm_log(const char* path) {
     return DGX_OK;
 }
 extern int g_dgx_dev_wgrad_lw;      // wgrad_lw.hip
-extern "C" int dgx_dev_set(const char* key, int value) {
+extern "C" int dgx_dev_set(const char* key, int value) {          // tests and A/B tools only; the values: dgxplan::DevKnobs
     if (!key) return DGX_ERR_BAD_ARG;
-    if (!strcmp(key, "gemm_lw")) g_dev.lw = value;                   // -1 plan, 0 gemm_nt everywhere, 1 gemm_lw everywhere
-    else if (!strcmp(key, "gemm_2wg")) g_dev.two_wg = value;         // -1 / 1 plan, 0 never the two-workgroup form, >= 2: its row threshold
-    else if (!strcmp(key, "gemm_tile")) { g_dev.tile_bm = value / 1000; g_dev.tile_bn = value % 1000; }     // bm * 1000 + bn, 0 = plan
-    else if (!strcmp(key, "gemm_splitk")) g_dev.splitk = value;      // 0 plan, >= 1 forced slab count
-    else if (!strcmp(key, "gemm_k192")) g_dev.k192 = value;          // -1 / 1 plan, 0 never the resident-panel kernel (gemm_k192.hip)
+    if (!strcmp(key, "gemm_lw")) g_dev.lw = value;
+    else if (!strcmp(key, "gemm_2wg")) g_dev.two_wg = value;
+    else if (!strcmp(key, "gemm_tile")) { g_dev.tile_bm = value / 1000; g_dev.tile_bn = value % 1000; }
+    else if (!strcmp(key, "gemm_splitk")) g_dev.splitk = value;
+    else if (!strcmp(key, "gemm_k192")) g_dev.k192 = value;
     else if (!strcmp(key, "wgrad_lw")) g_dgx_dev_wgrad_lw = value;   // 1 plan, 0 never the loader-wave form, 2 always
-    else if (!strcmp(key, "reset")) { g_dev = DevKnobs(); g_dgx_dev_wgrad_lw = 1; }
+    else if (!strcmp(key, "reset")) { g_dev = dgxplan::DevKnobs(); g_dgx_dev_wgrad_lw = 1; }
     else return DGX_ERR_BAD_ARG;
     return DGX_OK;
 }
@@ -583,7 +502,6 @@ extern "C" int dgx_gemm_bf16_nt(const void* A, const void* B, int M, int N, int 
     P.aux = (const uint16_t*)ep->aux; P.ldaux = (int)ep->ldaux;
     P.res = ep->residual; P.out = ep->out; P.scale = ep->scale; P.res_dtype = ep->residual_dtype;
     P.ws = (float*)ep->workspace;
-    g_ws_bytes_cur = ep->workspace ? ep->workspace_bytes : 0;
     P.relu = (ep->mode <= DGX_EPI_BIAS) ? ep->relu : 0;
     switch (ep->mode) {
         case DGX_EPI_NONE: case DGX_EPI_BIAS:
@@ -613,97 +531,16 @@ extern "C" int dgx_gemm_bf16_nt(const void* A, const void* B, int M, int N, int 
         }
         default: return DGX_ERR_BAD_ARG;
     }
-    hipStream_t st = (hipStream_t)stream;
-    const TileChoice tc = choose_tile(M, N);
     // algorithmic traffic: both operands once, every result tensor once (residual mode: residual in, sum out, no C)
     const double mn = (double)M * N, rsz = ep->residual_dtype == DGX_F32 ? 4.0 : 2.0;
     const double obytes = ep->mode == DGX_EPI_BIAS_RESIDUAL ? 2.0 * rsz * mn : (ep->mode >= DGX_EPI_BIAS_GELU ? 4.0 * mn : 2.0 * mn);   // GELU / GELU' / ReLU': two tensors
     DgxProfScope prof(DGX_PROF_GEMM_NT, stream, 2.0 * mn * K, 2.0 * ((double)M * K + (double)N * K) + obytes);
-    if (FILE* lf = gemm_log_file()) { fprintf(lf, "%d %d %d %d %d %d\n", M, N, K, ep->mode, (use_two_wg(P) && !use_lw(P)) ? 128 : tc.bm, tc.bn); fflush(lf); }
-    return dgx_gemm_dispatch(P, st);
+    return launch(P, plan_and_log(P, ep->workspace_bytes), (hipStream_t)stream);
 }
 
-bool dgx_gemm_k192_takes(const GemmP& P);              // gemm_k192.hip: the HBM-bound K = 192 problems of Swin stage 0
-int dgx_gemm_k192_launch(const GemmP& P, hipStream_t st);
-static int dgx_gemm_dispatch(GemmP& P, hipStream_t st) {
-    if (g_dev.k192 != 0 && g_dev.lw < 0 && g_dev.tile_bm == 0 && g_dev.splitk == 0 && g_dev.two_wg < 0 && dgx_gemm_k192_takes(P)) {
-        const int rc = dgx_gemm_k192_launch(P, st);
-        if (rc != DGX_ERR_UNSUPPORTED) {
-            g_last = {3, 32, 192, 1};
-            return rc;
-        }
-    }
-    const TileChoice tc = choose_tile(P.M, P.N);
-    if (use_lw(P)) return launch_lw(P, tc.bm, tc.bn, st);
-    if (tc.bn == 192) {
-        // contractions of up to 12 K-tiles (K <= 768: every qkv / proj / fc1 / fc2-input-gradient GEMM of the backbone) spend a third of
-        // a tile's time in prologue and read-out: TWO workgroups share a CU there (128 x 192 tiles, 2 stages = 80 KB of LDS, 128
-        // registers per lane), so one's read-out -- with its GELU / GELU' / residual tail -- runs beside the other's main loop.
-        // Round 2 measured this geometry back to back with the bias tail only (-4 % at K = 768, +10..30 % at long K) and dropped it;
-        // inside the step, where the tails are the real ones, it wins wherever K <= 768 (round 3, same call: GEMM family
-        // 11.80 -> 11.18 ms/step; K <= 384 only: 11.58; every K: 11.70) and loses on the long contractions, which keep the deeper rings.
-        // DGX_GEMM_2WG=0 switches it off (A/B).
-        if (use_two_wg(P)) {
-            switch (P.mode) {            // the tails this form exists for, each with its mode compiled in
-                case 2: return launch_gemm<128, 192, 2, 4, 2>(P, st);
-                case 3: return P.res_dtype == DGX_BF16 ? launch_gemm<128, 192, 2, 4, 3>(P, st) : launch_gemm<128, 192, 2, 4, 6>(P, st);
-                case 4: return launch_gemm<128, 192, 2, 4, 4>(P, st);
-                default: return launch_gemm<128, 192, 2, 4>(P, st);
-            }
-        }
-        if (tc.bm == 256) return launch_gemm<256, 192, 2>(P, st);
-        if (tc.bm == 192) return launch_gemm<192, 192, 3>(P, st);
-        return launch_gemm<128, 192, 4>(P, st);
-    }
-    if (tc.bn == 256 && tc.bm == 192) return launch_gemm<192, 256, 2>(P, st);
-    if (tc.bn == 256) return launch_gemm<128, 256, 3>(P, st);
-    if (tc.bm == 256) return launch_gemm<256, 128, 3>(P, st);
-    return launch_gemm<128, 128, 4>(P, st);
+extern "C" int64_t dgx_conv3x3_pad_rows(int N, int H, int W) {
+    return (N <= 0 || H <= 0 || W <= 0) ? 0 : (int64_t)N * (H + 2) * (W + 2) + 2 * (int64_t)(W + 3);
 }
-
-extern "C" int64_t dgx_conv3x3_pad_rows(int N, int H, int W);
-static int launch_lw_grouped(GemmP& P, const int* Ms, int n, int bm, int bn, hipStream_t st) {
-    P.tiles_n = (P.N + bn - 1) / bn;
-    int tot = 0;
-    for (int i = 0; i < n; ++i) {
-        P.grp[i].tile0 = tot;
-        tot += ((Ms[i] + bm - 1) / bm) * P.tiles_n;
-    }
-    P.total = tot;
-    P.splits = 1;
-    P.kt_per_split = (P.K + GBK - 1) / GBK;
-    P.per_xcd = (P.total + 7) / 8;
-    const int rc = gemm_lw_launch(P, bm, bn, st);
-    if (rc != DGX_OK) return rc;
-    g_last = {1, bm, bn, P.splits};
-    DGX_LAUNCH_CHECK();
-    return DGX_OK;
-}
-namespace {
-template <int BM, int BN, int NS, int MINW = 2>
-int launch_gemm_grouped(GemmP& P, const int* Ms, int n, hipStream_t st) {
-    using Cfg = GemmCfg<BM, BN, NS>;
-    P.tiles_n = (P.N + BN - 1) / BN;
-    int tot = 0;
-    for (int i = 0; i < n; ++i) {
-        P.grp[i].tile0 = tot;
-        tot += ((Ms[i] + BM - 1) / BM) * P.tiles_n;
-    }
-    P.total = tot;
-    P.splits = 1;
-    P.kt_per_split = (P.K + GBK - 1) / GBK;
-    P.per_xcd = (P.total + 7) / 8;
-    static bool once = false;
-    if (!once) {
-        if (hipFuncSetAttribute((const void*)gemm_nt_kernel<BM, BN, NS, MINW>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS) != hipSuccess)
-            return DGX_ERR_UNSUPPORTED;
-        once = true;
-    }
-    hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, NS, MINW>), dim3(8 * P.per_xcd), dim3(512), Cfg::LDS, st, P);
-    DGX_LAUNCH_CHECK();
-    return DGX_OK;
-}
-}  // namespace
 
 // y_i = conv3x3(x_i, w) (+ bias) for n <= 6 zero-bordered images that share the weights, in ONE launch (see GemmP::grp): the levels of
 // a CenterNet tower layer.  Cout <= 256 (one column tile of the instantiations used here).
@@ -711,7 +548,7 @@ extern "C" int dgx_conv3x3_gemm_multi(const dgx_conv_item* items, int n, const v
                                       void* stream) {
     if (n <= 0) return DGX_OK;
     if (!items || !w || Cin <= 0 || Cout <= 0 || (Cin & 63) || (Cout & 7)) return DGX_ERR_BAD_ARG;
-    if (n > dgxgemm::GEMM_MAXG || (int64_t)Cout * 9 * Cin * 2 >= (1ll << 31)) return DGX_ERR_UNSUPPORTED;
+    if (n > dgxgemm::GEMM_MAXG || Cout > 256 || (int64_t)Cout * 9 * Cin * 2 >= (1ll << 31)) return DGX_ERR_UNSUPPORTED;
     GemmP P;
     memset((void*)&P, 0, sizeof(P));
     P.B = (const uint16_t*)w;
@@ -722,14 +559,12 @@ extern "C" int dgx_conv3x3_gemm_multi(const dgx_conv_item* items, int n, const v
     P.conv_kc = Cin / GBK;
     P.relu = relu;
     P.ngrp = n;
-    int Ms[dgxgemm::GEMM_MAXG];
     double fl = 0.0, by = 2.0 * 9.0 * Cin * Cout;
     for (int i = 0; i < n; ++i) {
         const dgx_conv_item& a = items[i];
         if (!a.xpad || !a.y || a.N <= 0 || a.H <= 0 || a.W <= 0) return DGX_ERR_BAD_ARG;
         if (dgx_conv3x3_pad_rows(a.N, a.H, a.W) * Cin * 2 >= (1ll << 31)) return DGX_ERR_UNSUPPORTED;
-        Ms[i] = a.N * a.H * a.W;
-        P.grp[i].A = (const uint16_t*)a.xpad; P.grp[i].C = (uint16_t*)a.y; P.grp[i].M = Ms[i];
+        P.grp[i].A = (const uint16_t*)a.xpad; P.grp[i].C = (uint16_t*)a.y; P.grp[i].M = a.N * a.H * a.W;
         P.grp[i].cn = a.N; P.grp[i].ch = a.H; P.grp[i].cw = a.W; P.grp[i].wp = a.W + 2;
         const double pix = (double)a.N * a.H * a.W;
         fl += 2.0 * pix * Cout * 9.0 * Cin;
@@ -737,36 +572,10 @@ extern "C" int dgx_conv3x3_gemm_multi(const dgx_conv_item* items, int n, const v
     }
     for (int i = n; i < dgxgemm::GEMM_MAXG; ++i) P.grp[i] = P.grp[0];
     // first group's fields also in the single-image slots (the kernel overwrites them per tile)
-    P.A = P.grp[0].A; P.C = P.grp[0].C; P.M = Ms[0];
+    P.A = P.grp[0].A; P.C = P.grp[0].C; P.M = P.grp[0].M;
     P.cmap_n = P.grp[0].cn; P.cmap_h = P.grp[0].ch; P.cmap_w = P.grp[0].cw; P.conv_wp = P.grp[0].wp;
-    if (FILE* lf = gemm_log_file()) {              // one line per LAUNCH (tools/gemm_insitu.py joins lines with dispatches): M = all images' rows
-        int msum = 0;
-        for (int i = 0; i < n; ++i) msum += Ms[i];
-        int t128 = 0, t192 = 0;
-        for (int i = 0; i < n; ++i) { t128 += (Ms[i] + 127) / 128; t192 += (Ms[i] + 191) / 192; }
-        const bool big = Cout > 128 && tile_192x256() && ((t192 + 255) / 256) * 192 < ((t128 + 255) / 256) * 128;
-        fprintf(lf, "%d %d %d %d %d %d\n", msum, P.N, P.K, 9, big ? 192 : 128, Cout > 128 ? 256 : 128);
-        fflush(lf);
-    }
     DgxProfScope prof(DGX_PROF_GEMM_NT, stream, fl, by);
-    hipStream_t st = (hipStream_t)stream;
-    if (Cout > 256) return DGX_ERR_UNSUPPORTED;
-    if (Cout > 128) {
-        // 192-row tiles when they save a round of the chip (the five tower levels at 1024^2 x 2 images: 341 tiles of 128 rows =
-        // two rounds, 229 tiles of 192 rows = one)
-        int t128 = 0, t192 = 0;
-        for (int i = 0; i < n; ++i) { t128 += (Ms[i] + 127) / 128; t192 += (Ms[i] + 191) / 192; }
-        const bool big = tile_192x256() && ((t192 + 255) / 256) * 192 < ((t128 + 255) / 256) * 128;
-        if (g_dev.lw != 0) return launch_lw_grouped(P, Ms, n, big ? 192 : 128, 256, st);
-        if (big) return launch_gemm_grouped<192, 256, 2>(P, Ms, n, st);
-        return launch_gemm_grouped<128, 256, 3>(P, Ms, n, st);
-    }
-    if (g_dev.lw != 0) return launch_lw_grouped(P, Ms, n, 128, 128, st);
-    return launch_gemm_grouped<128, 128, 4>(P, Ms, n, st);
-}
-
-extern "C" int64_t dgx_conv3x3_pad_rows(int N, int H, int W) {
-    return (N <= 0 || H <= 0 || W <= 0) ? 0 : (int64_t)N * (H + 2) * (W + 2) + 2 * (int64_t)(W + 3);
+    return launch(P, plan_and_log(P, 0), (hipStream_t)stream);
 }
 
 extern "C" int dgx_conv3x3_gemm(const void* xpad, const void* w, const void* bias, void* y, int N, int H, int W, int Cin, int Cout,
@@ -787,15 +596,10 @@ extern "C" int dgx_conv3x3_gemm(const void* xpad, const void* w, const void* bia
     P.cmap_n = N; P.cmap_h = H; P.cmap_w = W;
     P.relu = relu;
     P.ws = (float*)workspace;                      // small FPN levels: few tiles, 9 Cin / 64 K-tiles -> split-K slabs + fold
-    g_ws_bytes_cur = workspace ? workspace_bytes : 0;
-    if (FILE* lf = gemm_log_file()) {
-        const TileChoice tc = choose_tile(P.M, P.N);
-        fprintf(lf, "%d %d %d %d %d %d\n", P.M, P.N, P.K, 9, tc.bm, tc.bn); fflush(lf);
-    }
     const double pix = (double)N * H * W;       // useful work: the H x W interior (border rows of the padded grid are overhead)
     DgxProfScope prof(DGX_PROF_GEMM_NT, stream, 2.0 * pix * Cout * 9.0 * Cin,
                       2.0 * ((double)Mp * Cin + 9.0 * Cin * Cout + pix * Cout));
-    return dgx_gemm_dispatch(P, (hipStream_t)stream);
+    return launch(P, plan_and_log(P, workspace_bytes), (hipStream_t)stream);
 }
 
 // Development timing hook (not part of include/divergen_hip.h): `iters` back-to-back launches of the same GEMM between two

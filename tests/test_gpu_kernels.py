@@ -1566,14 +1566,22 @@ def test_groupnorm_relu_multi_matches_per_tensor():
             assert float((a - c).abs().max()) <= 1e-4 * float(a.abs().max()) + 1e-6
 
 
-@pytest.mark.parametrize("Cin,Cout,top", [(256, 256, 32), (256, 64, 32), (64, 256, 32), (256, 256, 128)])
-def test_conv3x3_gemm_multi_equals_per_image(Cin, Cout, top):
+_MULTI_SHAPES = [(256, 256, 32), (256, 64, 32), (64, 256, 32), (256, 256, 128)]
+
+
+@pytest.mark.parametrize("Cin,Cout,top,form", [pytest.param(*c, None, id="%d-%d-%d" % c) for c in _MULTI_SHAPES] +
+                         [pytest.param(*c, "gemm_nt", id="%d-%d-%d-gemm_nt" % c) for c in _MULTI_SHAPES])
+def test_conv3x3_gemm_multi_equals_per_image(Cin, Cout, top, form, dgx_dev):
     """dgx_conv3x3_gemm_multi (the FPN levels of a tower layer in ONE grouped implicit-GEMM launch) against dgx_conv3x3_gemm image by
     image WITHOUT split-K (same K order per output element): bit-identical outputs, including the levels of 1-2 tiles and ragged M.
-    top = 128: the 1024^2 geometry, where the grouped launch takes 192-row tiles (one round instead of two)."""
+    top = 128: the 1024^2 geometry, where the grouped launch takes 192-row tiles (one round instead of two).
+    form: default dispatch (the loader-wave kernel) or dgx_dev("gemm_lw", 0): grouped launches on gemm_nt, which share its launch table
+    with the single-image ones; (256, 256, 128) is the only case that reaches the grouped 192 x 256 gemm_nt tile."""
     import ctypes
     from divergen_amd import _lib as L
     lib = L.lib()
+    if form == "gemm_nt":
+        dgx_dev("gemm_lw", 0)
     g = torch.Generator(device=DEV).manual_seed(Cin + Cout)
     shapes = [(2, top, top), (2, top // 2, top // 2), (2, top // 4, top // 4), (2, 5, 3), (1, 2, 2)]
     w = (torch.randn(Cout, 9 * Cin, device=DEV, generator=g) * 0.05).to(torch.bfloat16)
@@ -1597,6 +1605,10 @@ def test_conv3x3_gemm_multi_equals_per_image(Cin, Cout, top):
         items[i].xpad, items[i].y, items[i].N, items[i].H, items[i].W = L.ptr(xp), L.ptr(y), n, h, w_
         got.append(y)
     L.check(lib.dgx_conv3x3_gemm_multi(items, len(xs), L.ptr(w), L.ptr(b), Cin, Cout, 0, L.stream()), "conv multi")
+    if form == "gemm_nt":
+        bm, bn = L.c_i(), L.c_i()
+        assert lib.dgx_gemm_last_form(bm, bn, None) != 1, "the grouped launch ran on the loader-wave kernel"
+        assert (bm.value, bn.value) == ((192, 256) if top == 128 else (128, 256 if Cout > 128 else 128))
     for a, c in zip(ref, got):
         assert torch.equal(a.float(), c.float())
     # and against torch's convolution on the first level (fp32 accumulate both sides, bf16 output)

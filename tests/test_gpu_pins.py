@@ -105,7 +105,7 @@ def test_wgrad_lw_32_problems_and_ragged_contraction():
 NT, LW, TWO, K192 = 0, 1, 2, 3      # dgx_gemm_last_form: gemm_nt, gemm_lw (persistent loader-wave), gemm_nt two workgroups per CU, gemm_k192 (resident panel)
 # (M, N, K, mode, window map (B, H, W, ws, shift, residual dtype) or None, expected (form, bm, bn) under DEFAULT dispatch).
 # Shapes x tail modes: the top rows of profiles/r04_gemm_insitu.txt (>= 0.1 ms/step each; 9.6 of the family's 11.1 ms/step).
-# The expected form is this round's dispatch (csrc/gemm_nt.hip::use_lw / use_two_wg): when the dispatch changes, this table changes
+# The expected form is this round's dispatch (csrc/gemm_plan.h::plan_gemm): when the dispatch changes, this table changes
 # with it -- that is the point of the pin.
 BENCH_GEMMS = [
     (8192, 3072, 768, 4, None, None),                                   # fc2 input gradient x GELU'(f1), stage 2
