@@ -151,6 +151,10 @@ SIGNATURES = {
     "dgx_wgrad_grouped_form": (c_i, [ctypes.POINTER(WgradProblem), c_i]),
     "dgx_cascade_refine": (c_i, [c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_i, c_f, c_f, c_f, c_f, c_f,
                                  c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p]),
+    "dgx_ws_proposals": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_i, ctypes.c_double, c_p, c_p, c_p, c_p]),
+    "dgx_image_label_workspace_floats": (c_i64, [c_i, c_i]),
+    "dgx_image_label_loss": (c_i, [c_p, c_i64, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_i64,
+                                   c_p, c_i, c_p]),
     "dgx_paste_masks": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p]),
     "dgx_paste_rle": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
     "dgx_rle_encode": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),

@@ -128,6 +128,31 @@ def get_detection_dataset_dicts(names, filter_empty=True):
     return dicts
 
 
+def get_detection_dataset_dicts_with_source(names, filter_empty=True, dataset_ann=None):
+    """DG/divergen/data/custom_dataset_dataloader.py:333-365: the sources concatenated in the order of DATASETS.TRAIN, every dict
+    tagged with `dataset_source` = its source's position.  The reference filters images without box annotations over the whole
+    concatenation whenever the first dict has `annotations` -- which would silently delete every image-labelled source -- so
+    DATALOADER.FILTER_EMPTY_ANNOTATIONS is refused by name when a source is not 'box'."""
+    if isinstance(names, str):
+        names = [names]
+    assert len(names)
+    if dataset_ann is not None:
+        from ..config.image_labels import check_filter_empty
+        check_filter_empty(filter_empty, list(dataset_ann)[:len(names)])
+    dicts = []
+    for source, n in enumerate(names):
+        d = load_lvis_json(*dataset_files(n))
+        assert len(d), "Dataset '{}' is empty!".format(n)
+        for rec in d:
+            rec["dataset_source"] = source
+        dicts.extend(d)
+    if filter_empty:
+        before = len(dicts)
+        dicts = [d for d in dicts if any(a.get("iscrowd", 0) == 0 for a in d["annotations"])]
+        logger.info("Removed {} images with no usable annotations. {} images left.".format(before - len(dicts), len(dicts)))
+    return dicts
+
+
 # ----------------------------------------------------------------------------------------------- transforms
 class EfficientDetResizeCropTransform:
     """custom_transform.py:27-91 (uint8 images through PIL, coordinates scaled then shifted)."""
@@ -416,6 +441,14 @@ class DatasetMapper:
             else:
                 augmentations = [ResizeShortestEdge(cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST, "choice")]
         self.augmentations = augmentations
+        # WITH_IMAGE_LABELS (DG custom_dataset_mapper.py:55-69, :108-117, :166-170): `ann_type` / `pos_category_ids` on every sample;
+        # with USE_DIFF_BS_SIZE one EfficientDetResizeCrop per source
+        self.with_ann_type = bool(cfg.WITH_IMAGE_LABELS)
+        self.dataset_ann = list(cfg.DATALOADER.DATASET_ANN)
+        self.dataset_augs = None
+        if cfg.DATALOADER.USE_DIFF_BS_SIZE and is_train:       # (another CUSTOM_AUG: build_custom_augmentation has refused it above)
+            self.dataset_augs = [[EfficientDetResizeCrop(size, tuple(scale)), RandomFlip()]
+                                 for scale, size in zip(cfg.DATALOADER.DATASET_INPUT_SCALE, cfg.DATALOADER.DATASET_INPUT_SIZE)]
         self.image_format = cfg.INPUT.FORMAT
         self.use_instance_mask = cfg.MODEL.MASK_ON
         if cfg.INPUT.MASK_FORMAT != "bitmask" and cfg.MODEL.MASK_ON and is_train:
@@ -430,7 +463,8 @@ class DatasetMapper:
         d.setdefault("width", image.shape[1])
         d.setdefault("height", image.shape[0])
         transforms = []
-        for aug in self.augmentations:
+        augs = self.augmentations if self.dataset_augs is None else self.dataset_augs[d["dataset_source"]]
+        for aug in augs:
             t = aug.get_transform(image)
             image = t.apply_image(image)
             transforms.append(t)
@@ -450,6 +484,9 @@ class DatasetMapper:
             if not inst.has("gt_masks"):
                 inst.gt_masks = BitMasks(torch.zeros(0, image_shape[0], image_shape[1], dtype=torch.bool))
             d["instances"] = inst
+        if self.with_ann_type:
+            d["pos_category_ids"] = d.get("pos_category_ids", [])
+            d["ann_type"] = self.dataset_ann[d["dataset_source"]]
         return d
 
 
@@ -635,6 +672,10 @@ class CopyPasteMapper:
         flip / placement packed for the compositor (InstPool.prepare), BSGAL's held-out image.  CPU tensors only."""
         result = self.mapper(dataset_dict)
         if "instances" not in result or not result["instances"].has("gt_masks"):        # mapper.py:862-864
+            return result
+        if result.get("ann_type", "box") != "box":
+            # an image-labelled sample: in the reference it has no annotations, hence no gt_masks, and leaves at :862-864 before any
+            # draw; here it carries EMPTY instances (with an empty mask stack), so it leaves by its annotation type
             return result
         if self.rm_bg_prob > 0 and np.random.uniform(0.0, 1.0) <= self.rm_bg_prob:      # mapper.py:869-872; the pixels: finish()
             result = dict(result, rm_bg=True)
@@ -1095,11 +1136,25 @@ def build_detection_train_loader(cfg, per_gpu, device, seed):
     sample written by its worker into a slot of a page-locked shared-memory ring (SlotRing; the DataLoader's pin thread when the ring
     cannot be had); the training process only uploads and runs the compositor kernel, one batch ahead on a side stream (BatchAhead)."""
     import functools
-    dicts = get_detection_dataset_dicts(cfg.DATASETS.TRAIN, filter_empty=cfg.DATALOADER.FILTER_EMPTY_ANNOTATIONS)
+    from ..config.image_labels import check_loader_keys
     name = cfg.DATALOADER.SAMPLER_TRAIN
-    if name == "TrainingSampler":
+    check_loader_keys(cfg, per_gpu)
+    batch_sizes = None          # MultiDatasetSampler: the per-source sizes of its grouped batches
+    if name == "MultiDatasetSampler":
+        from .samplers import GroupedBatchSampler, MultiDatasetSampler
+        n_src = len(cfg.DATASETS.TRAIN)
+        dicts = get_detection_dataset_dicts_with_source(cfg.DATASETS.TRAIN, filter_empty=cfg.DATALOADER.FILTER_EMPTY_ANNOTATIONS,
+                                                        dataset_ann=cfg.DATALOADER.DATASET_ANN)
+        sampler = MultiDatasetSampler(dicts, list(cfg.DATALOADER.DATASET_RATIO)[:n_src], list(cfg.DATALOADER.USE_RFS)[:n_src],
+                                      list(cfg.DATALOADER.DATASET_ANN)[:n_src], cfg.DATALOADER.REPEAT_THRESHOLD, seed=seed)
+        batch_sizes = [int(b) for b in list(cfg.DATALOADER.DATASET_BS)[:n_src]] if cfg.DATALOADER.USE_DIFF_BS_SIZE else [int(per_gpu)]
+        sampler = GroupedBatchSampler(sampler, dicts, batch_sizes)
+        per_gpu = max(batch_sizes)          # the slot ring is sized for the largest batch
+    elif name == "TrainingSampler":
+        dicts = get_detection_dataset_dicts(cfg.DATASETS.TRAIN, filter_empty=cfg.DATALOADER.FILTER_EMPTY_ANNOTATIONS)
         sampler = TrainingSampler(len(dicts), seed=seed)
     elif name == "RepeatFactorTrainingSampler":
+        dicts = get_detection_dataset_dicts(cfg.DATASETS.TRAIN, filter_empty=cfg.DATALOADER.FILTER_EMPTY_ANNOTATIONS)
         rf = RepeatFactorTrainingSampler.repeat_factors_from_category_frequency(dicts, cfg.DATALOADER.REPEAT_THRESHOLD)
         sampler = RepeatFactorTrainingSampler(rf, seed=seed)
     else:
@@ -1127,8 +1182,9 @@ def build_detection_train_loader(cfg, per_gpu, device, seed):
             logger.warning("loader: no page-locked slot ring (%s); falling back to the DataLoader's pin thread", e)
             pin_thread = True
     mapper.ring = ring
+    how = dict(batch_sampler=sampler) if batch_sizes is not None else dict(sampler=sampler, batch_size=per_gpu, drop_last=True)
     loader = torch.utils.data.DataLoader(
-        _MapDataset(dicts, mapper), sampler=sampler, batch_size=per_gpu, drop_last=True, num_workers=nw,
+        _MapDataset(dicts, mapper), num_workers=nw, **how,
         collate_fn=_RingCollate(ring) if ring is not None else _identity,
         worker_init_fn=functools.partial(_worker_init, base_seed=rank_seed, pool=mapper.inst_pool), pin_memory=pin_thread,
         prefetch_factor=cfg.DATALOADER.PREFETCH_FACTOR if nw > 0 else None, persistent_workers=nw > 0)

@@ -87,6 +87,88 @@ class RepeatFactorTrainingSampler(_SeededStream):
         return torch.repeat_interleave(torch.arange(counts.numel()), counts)
 
 
+def repeat_factors_from_tag_frequency(dataset_dicts, repeat_thresh):
+    """DG/divergen/data/custom_dataset_dataloader.py:481-504: the repeat factors of an image-labelled source, from the frequency of
+    its `pos_category_ids` instead of box annotations; an image without labels gets 1."""
+    freq = {}
+    for d in dataset_dicts:
+        for cid in d["pos_category_ids"]:
+            freq[cid] = freq.get(cid, 0) + 1
+    n = len(dataset_dicts)
+    cat_rep = {cid: max(1.0, math.sqrt(repeat_thresh / (cnt / n))) for cid, cnt in freq.items()}
+    return torch.tensor([max({cat_rep[cid] for cid in d["pos_category_ids"]}, default=1.0) for d in dataset_dicts], dtype=torch.float32)
+
+
+class MultiDatasetSampler:
+    """DG/divergen/data/custom_dataset_dataloader.py:368-438: indices into the CONCATENATION of several sources (`dataset_source` on
+    every dict, sources back to back), drawn with replacement.  Image i of source s weighs max(sizes) / size_s * ratio_s / sum(ratio)
+    times its repeat factor; with USE_RFS[s] that is the category-frequency factor of a 'box' source and the tag-frequency factor of
+    any other, rescaled to sum to size_s.  One `torch.multinomial(weights, N, replacement=True)` per pass on the shared seeded
+    generator, every world_size-th index starting at the rank."""
+
+    def __init__(self, dataset_dicts, dataset_ratio, use_rfs, dataset_ann, repeat_threshold=0.001, seed=None, rank=None, world_size=None):
+        n_src = len(dataset_ratio)
+        sizes = [0] * n_src
+        for d in dataset_dicts:
+            sizes[d["dataset_source"]] += 1
+        if min(sizes) == 0:
+            raise ValueError("MultiDatasetSampler: dataset sizes %s for %d DATALOADER.DATASET_RATIO entries" % (sizes, n_src))
+        self.sizes = sizes
+        self.seed = int(comm.shared_random_seed() if seed is None else seed)
+        self.rank = comm.get_rank() if rank is None else int(rank)
+        self.world = comm.get_world_size() if world_size is None else int(world_size)
+        self.dataset_ids = torch.tensor([d["dataset_source"] for d in dataset_dicts], dtype=torch.long)
+        weight = torch.cat([torch.ones(s) * max(sizes) / s * r / sum(dataset_ratio) for r, s in zip(dataset_ratio, sizes)])
+        factors, st = [], 0
+        for i, s in enumerate(sizes):
+            if use_rfs[i]:
+                fn = RepeatFactorTrainingSampler.repeat_factors_from_category_frequency if dataset_ann[i] == "box" \
+                    else repeat_factors_from_tag_frequency
+                f = fn(dataset_dicts[st:st + s], repeat_threshold)
+                f = f * (s / f.sum())
+            else:
+                f = torch.ones(s)
+            factors.append(f)
+            st += s
+        self.weights = weight * torch.cat(factors)
+
+    def stream(self):
+        gen = torch.Generator().manual_seed(self.seed)
+        while True:
+            yield from torch.multinomial(self.weights, len(self.weights), generator=gen, replacement=True).tolist()
+
+    def __iter__(self):
+        return _rank_share(self.stream(), self.rank, self.world)
+
+
+class GroupedBatchSampler:
+    """The batches of MDAspectRatioGroupedDataset / DIFFMDAspectRatioGroupedDataset (custom_dataset_dataloader.py:441-478) formed
+    BEFORE the samples are mapped: a batch sampler over the rank's index stream.  Index i goes to bucket
+    `dataset_source * 2 + (0 if width > height else 1)` of its dataset dict; a bucket is emitted, in arrival order, when it holds
+    the batch size -- `batch_sizes[source]` (USE_DIFF_BS_SIZE: DATALOADER.DATASET_BS) or the one per-GPU size.  Same composition
+    and order as grouping the mapped samples, and a batch never mixes sources, so it never mixes annotation types."""
+
+    def __init__(self, sampler, dataset_dicts, batch_sizes):
+        self.sampler = sampler
+        self.bucket_of = [d["dataset_source"] * 2 + (0 if d["width"] > d["height"] else 1) for d in dataset_dicts]
+        self.batch_sizes = [int(b) for b in batch_sizes]
+        n_src = max(d["dataset_source"] for d in dataset_dicts) + 1
+        if len(self.batch_sizes) == 1:
+            self.batch_sizes = self.batch_sizes * n_src
+        if len(self.batch_sizes) < n_src or min(self.batch_sizes) < 1:
+            raise ValueError("GroupedBatchSampler: batch sizes %s for %d sources" % (batch_sizes, n_src))
+
+    def __iter__(self):
+        buckets = {}
+        for i in self.sampler:
+            b = self.bucket_of[i]
+            bucket = buckets.setdefault(b, [])
+            bucket.append(i)
+            if len(bucket) == self.batch_sizes[b // 2]:
+                yield bucket[:]
+                del bucket[:]
+
+
 class InferenceSampler:
     """Contiguous shards of range(size), sizes differing by at most one (the first size % world ranks take the extra)."""
 

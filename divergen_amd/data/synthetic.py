@@ -88,3 +88,29 @@ def write_mini_lvis(root, n_images=32, image_hw=(480, 640), n_obj=12, n_pool=64,
     with open(os.path.join(root, "pool.json"), "w") as f:
         json.dump(pool, f)
     return {"root": root, "pool_json": os.path.join(root, "pool.json"), "n_images": n_images, "n_pool": n_pool}
+
+
+def write_mini_image_labels(root, split="imagenet_lvis_mini", n_images=8, image_hw=(120, 160), n_cats=1203, seed=0):
+    """A small IMAGE-LABELLED source in the ImageNet-LVIS json format (WITH_IMAGE_LABELS): `root`/imagenet/<split>/*.jpg and
+    `root`/imagenet/<split>.json whose images carry `pos_category_ids` (1-based LVIS category ids, one to three per image) and no
+    annotations; every second image is portrait.  Returns dict(json, image_root, n_images); register it with
+    data.build.register_lvis_instances(name, json, image_root).  Deterministic in `seed`."""
+    import json
+    import os
+    from PIL import Image
+    rng = np.random.default_rng(seed)
+    image_root = os.path.join(root, "imagenet", split)
+    os.makedirs(image_root, exist_ok=True)
+    H, W = image_hw
+    images = []
+    for i in range(n_images):
+        h, w = (H, W) if i % 2 == 0 else (W, H)
+        low = rng.integers(0, 256, (max(h // 32, 2), max(w // 32, 2), 3), dtype=np.uint8)
+        Image.fromarray(low).resize((w, h), Image.BICUBIC).save(os.path.join(image_root, "%08d.jpg" % (i + 1)), quality=90)
+        pos = sorted(set(int(c) for c in rng.integers(1, n_cats + 1, int(rng.integers(1, 4)))))
+        images.append({"id": i + 1, "height": h, "width": w, "file_name": "%08d.jpg" % (i + 1), "pos_category_ids": pos})
+    cats = [{"id": c, "name": "c%d" % c} for c in range(1, n_cats + 1)]
+    path = os.path.join(root, "imagenet", split + ".json")
+    with open(path, "w") as f:
+        json.dump({"images": images, "annotations": [], "categories": cats}, f)
+    return {"json": path, "image_root": image_root, "n_images": n_images}

@@ -19,7 +19,10 @@ therefore learns the number of signals per parameter from the first step (during
 afterwards counts a parameter as ready at its last expected signal.  The counts depend on HOW the hipGraph segments ran in a step
 (a replayed segment signals each parameter once behind the replay, an eagerly issued one once per use; a segment runs eagerly on
 the first sight of a batch size and on sizes beyond utils.graphs.MAX_GRAPHS), so one count vector is learned per combination of
-segment modes (layers.linear_ops.SEGMENT_MODES), each in a step of its own without early launches.  Fewer signals than learned (a hipGraph replay
+segment modes (layers.linear_ops.SEGMENT_MODES), each in a step of its own without early launches.  With WITH_IMAGE_LABELS the
+counts also depend on the step's ANNOTATION TYPE (an image-labelled step runs no mask head, no proposal losses and the box stages as
+composed modules; ranks may be on different types in the same iteration): the trainer announces it (`step_kind`) and the vector
+is keyed by it as well -- a vector learned on an image step would otherwise be held against the next box step.  Fewer signals than learned (a hipGraph replay
 produces none, a branch not taken) only defer the bucket to `finish()`; MORE signals than learned would mean a bucket
 could have left before its gradients were complete, and `finish()` raises."""
 import os
@@ -65,6 +68,7 @@ class ArenaReducer:
         self._learned = {}             # segment-mode combination -> learned signal counts
         self._expected = None          # this step's counts; None = calibrating (no early launches)
         self._mode_key = None          # taken at the step's first signal (every segment has run its forward by then)
+        self.step_kind = None          # the step's annotation type ('box' | 'image'), set by a WITH_IMAGE_LABELS trainer before backward
         # single_rank_group: reduce over a one-rank group as well (bench.py --force-pg: RCCL next to hipGraph capture on one GPU)
         self.active = self.world > 1 or (dist.is_initialized() and single_rank_group)
         self.reserved_cus = 0
@@ -97,6 +101,11 @@ class ArenaReducer:
                 # AccumulateGrad and call this instead
                 p._dgx_ready = (lambda h=hook: h(None))
 
+    def _step_key(self):
+        """What this step's signal counts are filed under: the segment modes, and the announced annotation type when there is one."""
+        key = tuple(sorted(linear_ops.SEGMENT_MODES.items()))
+        return key if self.step_kind is None else key + (("ann_type", self.step_kind),)
+
     def _reserve(self, on):
         if self.arena.g.is_cuda:
             from .. import _lib as L
@@ -115,7 +124,7 @@ class ArenaReducer:
             if linear_ops._READY_SUSPENDED[0]:     # trial backward passes (hipGraph capture warm-ups, BSGAL's selection) are not
                 return                             # part of the training step: nothing to count, nothing to reduce
             if self._mode_key is None:
-                self._mode_key = tuple(sorted(linear_ops.SEGMENT_MODES.items()))
+                self._mode_key = self._step_key()
                 self._expected = self._learned.get(self._mode_key)
             self._got[i] += 1
             if self._expected is not None and self._got[i] == self._expected[i]:
@@ -177,7 +186,7 @@ class ArenaReducer:
             self._reserve(False)
         if self.active:
             if self._mode_key is None:
-                self._mode_key = tuple(sorted(linear_ops.SEGMENT_MODES.items()))
+                self._mode_key = self._step_key()
                 self._expected = self._learned.get(self._mode_key)
             if self._expected is None:
                 self._learned[self._mode_key] = list(self._got)

@@ -1,5 +1,6 @@
 """CustomRCNN meta-architecture.  Mirrors DG/divergen/modeling/meta_arch/custom_rcnn.py:24-207 over
-D2/modeling/meta_arch/rcnn.py:24-243 for the box-supervised path the shipped configs train.
+D2/modeling/meta_arch/rcnn.py:24-243 for the box-supervised path the shipped configs train and, with WITH_IMAGE_LABELS, for
+batches that carry image labels only (:128-136, :190-202).
 
 Precision: the reference runs the backbone under fp16 autocast + GradScaler and the heads in fp32
 (custom_rcnn.py:141-146).  This build has ONE precision: bf16 operands, fp32 accumulation in every GEMM / convolution /
@@ -101,11 +102,12 @@ class EarlyLosses(dict):
 class CustomRCNN(nn.Module):
     @configurable
     def __init__(self, *, backbone, proposal_generator, roi_heads, pixel_mean, pixel_std, input_format=None,
-                 vis_period=0, fp16=False, with_image_labels=False, roi_head_name="", **unused):
+                 vis_period=0, fp16=False, with_image_labels=False, roi_head_name="", dataset_loss_weight=(), **unused):
         super().__init__()
         assert proposal_generator is not None
-        if with_image_labels:
-            raise NotImplementedError("WITH_IMAGE_LABELS co-training is outside the shipped configs")
+        # WITH_IMAGE_LABELS: every sample carries `ann_type` ('box' | 'image') and `pos_category_ids`, a batch holds one type
+        self.with_image_labels = bool(with_image_labels)
+        self.dataset_loss_weight = [float(w) for w in dataset_loss_weight]      # MODEL.DATASET_LOSS_WEIGHT, by `dataset_source`
         self.backbone, self.proposal_generator, self.roi_heads = backbone, proposal_generator, roi_heads
         self.input_format, self.vis_period, self.fp16, self.roi_head_name = input_format, vis_period, fp16, roi_head_name
         self.register_buffer("pixel_mean", torch.tensor(pixel_mean).view(-1, 1, 1), False)
@@ -132,7 +134,8 @@ class CustomRCNN(nn.Module):
         return dict(backbone=backbone, proposal_generator=build_proposal_generator(cfg, shape),
                     roi_heads=build_roi_heads(cfg, shape), input_format=cfg.INPUT.FORMAT, vis_period=cfg.VIS_PERIOD,
                     pixel_mean=cfg.MODEL.PIXEL_MEAN, pixel_std=cfg.MODEL.PIXEL_STD, fp16=cfg.FP16,
-                    with_image_labels=cfg.WITH_IMAGE_LABELS, roi_head_name=cfg.MODEL.ROI_HEADS.NAME)
+                    with_image_labels=cfg.WITH_IMAGE_LABELS, roi_head_name=cfg.MODEL.ROI_HEADS.NAME,
+                    dataset_loss_weight=cfg.MODEL.DATASET_LOSS_WEIGHT)
 
     @property
     def device(self):
@@ -180,14 +183,63 @@ class CustomRCNN(nn.Module):
             return losses
         return self.training_losses(batched_inputs, early=self.early_proposal_backward and not self.return_proposal)
 
+    def _annotation_type(self, batched_inputs, gt_instances):
+        """custom_rcnn.py:128-136: the batch's one annotation type; `ann_type` / `pos_category_ids` copied onto the instances."""
+        if not self.with_image_labels:
+            return "box"
+        for inst, x in zip(gt_instances, batched_inputs):
+            if "ann_type" not in x or "pos_category_ids" not in x:
+                raise KeyError("WITH_IMAGE_LABELS: every sample needs 'ann_type' and 'pos_category_ids' (the loader's mapper adds them)")
+            inst._ann_type, inst._pos_category_ids = x["ann_type"], x["pos_category_ids"]
+        types = set(x["ann_type"] for x in batched_inputs)
+        assert len(types) == 1, "one annotation type per batch, got %s (DATALOADER.MULTI_DATASET_GROUPING)" % sorted(types)
+        ann_type = types.pop()
+        if ann_type not in ("box", "image"):
+            raise NotImplementedError("ann_type %r: 'box' and 'image' are built (DATALOADER.DATASET_ANN)" % (ann_type,))
+        return ann_type
+
+    def _weight_by_source(self, batched_inputs, losses):
+        """custom_rcnn.py:197-202: MODEL.DATASET_LOSS_WEIGHT multiplies every loss by the weight of the batch's `dataset_source`."""
+        if not self.dataset_loss_weight:
+            return losses
+        sources = set(x["dataset_source"] for x in batched_inputs)
+        assert len(sources) == 1, "one dataset_source per batch, got %s" % sorted(sources)
+        w = self.dataset_loss_weight[sources.pop()]
+        for k in list(losses.keys()):
+            losses[k] = losses[k] * w
+        return losses
+
+    def _image_step_losses(self, images, features, gt_instances):
+        """An image-labelled batch (custom_rcnn.py:166-194): the proposal generator runs for its proposals only, without gradient
+        tracking (no autograd graph is built or held) -- its losses are reported as exact zeros (the reference's `v * 0` of finite
+        values), so neither its backward nor the early backward pass exist in this step; the RoI heads train the cascade's
+        classifiers on the image labels."""
+        with torch.no_grad():
+            proposals, proposal_losses = self.proposal_generator(images, features, gt_instances)
+        proposals, detector_losses = self.roi_heads(images, features, proposals, gt_instances, ann_type="image")
+        losses = dict(detector_losses)
+        losses.update({k: v.detach().float().reshape(()) * 0.0 for k, v in proposal_losses.items()})
+        return proposals, losses
+
     def training_losses(self, batched_inputs, only_gt_proposals=False, early=False):
         """custom_rcnn.py:118-207 for the box-supervised path: the loss dict of one batch."""
         images = self.preprocess_image(batched_inputs)
         gt_instances = [x["instances"].to(self.device) for x in batched_inputs]
+        ann_type = self._annotation_type(batched_inputs, gt_instances)
+        early = early and not self.dataset_loss_weight      # (a weighted loss cannot have been back-propagated unweighted)
         features = self._features(images)
         from ...solver import join_transposes
         join_transposes()        # transposed weight images refreshed beside the backbone forward: first read by what follows
         grads_on = torch.is_grad_enabled() and all(f.requires_grad for f in features.values())
+        if ann_type == "image":
+            if only_gt_proposals:
+                raise NotImplementedError("only_gt_proposals (BSGAL's held-out pass) on an image-labelled batch")
+            with torch.autocast("cuda", dtype=torch.bfloat16):
+                if grads_on:
+                    fg, features = _shared_gradient_maps(features)
+                proposals, losses = self._image_step_losses(images, features, gt_instances)
+            losses = self._weight_by_source(batched_inputs, losses)
+            return (proposals, losses) if self.return_proposal else losses
         with torch.autocast("cuda", dtype=torch.bfloat16):
             if grads_on:
                 # the consumers of the FPN levels write ONE gradient map per level between them
@@ -232,6 +284,7 @@ class CustomRCNN(nn.Module):
         losses = EarlyLosses() if (early and grads_on) else {}
         losses.update(detector_losses)
         losses.update(proposal_losses)
+        losses = self._weight_by_source(batched_inputs, losses)
         if isinstance(losses, EarlyLosses):
             self.__dict__["_early_outstanding"] = losses
         return (proposals, losses) if self.return_proposal else losses

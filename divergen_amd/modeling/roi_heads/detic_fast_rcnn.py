@@ -167,8 +167,13 @@ class DeticFastRCNNOutputLayers(nn.Module):
                  loss_weight=1.0, mult_proposal_score=False, use_sigmoid_ce=False, use_fed_loss=False,
                  ignore_zero_cats=False, fed_loss_num_cat=50, prior_prob=0.01, cat_freq_path="",
                  fed_loss_freq_weight=0.5, use_zeroshot_cls=False, cls_score=None, divergen_box_loss=True, only_paste_sup=False,
-                 **unused):
+                 image_label_loss="", image_loss_weight=0.1, add_image_box=False, **unused):
         super().__init__()
+        # WITH_IMAGE_LABELS (DG detic_fast_rcnn.py:342-434): "" = the predictor trains on box annotations only
+        if image_label_loss:
+            from ...config.image_labels import check_image_label_loss
+            check_image_label_loss(image_label_loss, add_image_box, use_sigmoid_ce)
+        self.image_label_loss, self.image_loss_weight, self.add_image_box = image_label_loss, float(image_loss_weight), add_image_box
         if box_reg_loss_type != "smooth_l1":
             raise NotImplementedError("MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE %r: only 'smooth_l1' is built (the shipped configs)"
                                       % (box_reg_loss_type,))
@@ -215,12 +220,14 @@ class DeticFastRCNNOutputLayers(nn.Module):
     @classmethod
     def from_config(cls, cfg, input_shape, box2box_transform=None):
         h = cfg.MODEL.ROI_BOX_HEAD
+        from ...config.image_labels import check_model_keys
+        check_model_keys(cfg)
         if h.USE_ZEROSHOT_CLS:
             for key, on in (("MODEL.ROI_BOX_HEAD.WITH_SOFTMAX_PROP", h.WITH_SOFTMAX_PROP), ("MODEL.DYNAMIC_CLASSIFIER", cfg.MODEL.DYNAMIC_CLASSIFIER),
                             ("MODEL.WITH_CAPTION", cfg.MODEL.WITH_CAPTION)):
                 if on:
-                    raise NotImplementedError("%s is not built: the open-vocabulary classifier trains on box annotations only "
-                                              "(no proposal-score branch, dynamic classifier, caption or image-label losses)" % key)
+                    raise NotImplementedError("%s is not built: the open-vocabulary classifier trains on box annotations and image labels "
+                                              "(no proposal-score branch, dynamic classifier or caption losses)" % key)
         return dict(input_shape=input_shape, cls_score=ZeroShotClassifier(cfg, input_shape) if h.USE_ZEROSHOT_CLS else None,
                     box2box_transform=box2box_transform or Box2BoxTransform(weights=h.BBOX_REG_WEIGHTS),
                     num_classes=cfg.MODEL.ROI_HEADS.NUM_CLASSES, cls_agnostic_bbox_reg=h.CLS_AGNOSTIC_BBOX_REG,
@@ -231,7 +238,9 @@ class DeticFastRCNNOutputLayers(nn.Module):
                     fed_loss_num_cat=h.FED_LOSS_NUM_CAT, prior_prob=h.PRIOR_PROB, cat_freq_path=h.CAT_FREQ_PATH,
                     fed_loss_freq_weight=h.FED_LOSS_FREQ_WEIGHT, use_zeroshot_cls=h.USE_ZEROSHOT_CLS,
                     divergen_box_loss=cfg.MODEL.USE_DIVERGEN_BOX_LOSS and cfg.MODEL.get("USE_XPASTE_BOX_LOSS", True),
-                    only_paste_sup=cfg.MODEL.get("ONLY_PASTE_SUP", False))
+                    only_paste_sup=cfg.MODEL.get("ONLY_PASTE_SUP", False),
+                    image_label_loss=h.IMAGE_LABEL_LOSS if cfg.WITH_IMAGE_LABELS else "", image_loss_weight=h.IMAGE_LOSS_WEIGHT,
+                    add_image_box=h.ADD_IMAGE_BOX)
 
     def forward(self, x, classifier_info=(None, None, None)):
         if x.dim() > 2:
@@ -353,6 +362,24 @@ class DeticFastRCNNOutputLayers(nn.Module):
         if self.only_paste_sup and paste_src is not None and self.use_sigmoid_ce and scores.numel():
             losses["loss_paste_ins"], losses["loss_nopaste_ins"] = self.paste_split(scores, gt_classes, w, paste_src)
         return losses
+
+    def image_label_losses(self, scores, valid, boxes, counts, image_sizes, image_labels, csr=None):
+        """DG detic_fast_rcnn.py:342-434 for one cascade stage of an image-labelled batch: one launch selects a row per (image, label),
+        sums the sigmoid BCE of the selected rows and leaves the logged statistics on the device (dgx_image_label_loss); loss_cls and
+        loss_box_reg are the reference's exact zeros.  scores (R, C+1) may be the strided column slice of the joint predictor output."""
+        from ...layers.image_label_ops import image_label_loss
+        if not self.image_label_loss:
+            raise RuntimeError("image_label_losses on a predictor built without WITH_IMAGE_LABELS")
+        with torch.autocast("cuda", enabled=False):
+            loss, out, _ = image_label_loss(scores, valid, boxes, counts, image_sizes, image_labels, self.image_label_loss,
+                                            self.image_loss_weight, csr=csr)
+        st = get_event_storage()
+        from ...utils.events import DeferredScalar
+        st.put_scalar("stats_l_image", DeferredScalar(lambda o: o[1], out))
+        for i, name in enumerate(("pool_stats", "stats_select_size", "stats_select_x", "stats_select_y", "stats_max_label_score")):
+            st.put_scalar(name, DeferredScalar(lambda o, i=i: o[2 + i], out))
+        zero = torch.zeros((), dtype=torch.float32, device=scores.device)
+        return {"image_loss": loss, "loss_cls": zero, "loss_box_reg": zero.clone()}
 
     def no_grad_losses(self, predictions, proposals, classifier_info=(None, None, None)):
         """BS detic_fast_rcnn.py:268-352 for the sigmoid-CE recipe: the losses of the held-out pass over ground-truth

@@ -101,8 +101,14 @@ class DeticCascadeROIHeads(nn.Module):
     def __init__(self, *, num_classes, batch_size_per_image, positive_fraction, proposal_append_gt, box_in_features,
                  box_pooler, box_heads, box_predictors, cascade_ious, mask_in_features=None, mask_pooler=None,
                  mask_head=None, mult_proposal_score=False, mask_weight=1.0, divergen_mask_loss=True,
-                 one_class_per_proposal=False, **unused):
+                 one_class_per_proposal=False, with_image_labels=False, add_image_box=False, image_box_size=1.0, ws_num_props=128,
+                 **unused):
         super().__init__()
+        # WITH_IMAGE_LABELS (DG detic_roi_heads.py:192-244, :309-365): image-labelled batches train the cascade through _forward_image
+        self.with_image_labels, self.add_image_box = with_image_labels, add_image_box
+        self.image_box_size, self.ws_num_props = float(image_box_size), int(ws_num_props)
+        if with_image_labels and self.ws_num_props + (1 if add_image_box else 0) <= 0:
+            raise ValueError("MODEL.ROI_BOX_HEAD.WS_NUM_PROPS %d without ADD_IMAGE_BOX leaves an image step without proposals" % ws_num_props)
         self.num_classes, self.batch_size_per_image, self.positive_fraction = num_classes, batch_size_per_image, positive_fraction
         self.proposal_append_gt = proposal_append_gt
         self.box_in_features, self.box_pooler = box_in_features, box_pooler
@@ -135,7 +141,9 @@ class DeticCascadeROIHeads(nn.Module):
                    box_pooler=ROIPooler(bh.POOLER_RESOLUTION, scales, bh.POOLER_SAMPLING_RATIO, bh.POOLER_TYPE, out_nhwc=True),
                    box_heads=heads, box_predictors=preds, cascade_ious=ch.IOUS,
                    mult_proposal_score=bh.MULT_PROPOSAL_SCORE, mask_weight=rh.MASK_WEIGHT,
-                   divergen_mask_loss=cfg.MODEL.USE_DIVERGEN_MASK_LOSS and cfg.MODEL.get("USE_XPASTE_MASK_LOSS", True), one_class_per_proposal=rh.ONE_CLASS_PER_PROPOSAL)
+                   divergen_mask_loss=cfg.MODEL.USE_DIVERGEN_MASK_LOSS and cfg.MODEL.get("USE_XPASTE_MASK_LOSS", True), one_class_per_proposal=rh.ONE_CLASS_PER_PROPOSAL,
+                   with_image_labels=cfg.WITH_IMAGE_LABELS, add_image_box=bh.ADD_IMAGE_BOX, image_box_size=bh.IMAGE_BOX_SIZE,
+                   ws_num_props=bh.WS_NUM_PROPS)
         if cfg.MODEL.MASK_ON:
             mh = cfg.MODEL.ROI_MASK_HEAD
             ret.update(mask_in_features=in_features,
@@ -522,9 +530,81 @@ class DeticCascadeROIHeads(nn.Module):
             x = self.mask_pooler(feats, boxes, pad_to=64 if self.training else 0)
         return self.mask_head(x, instances)
 
-    def forward(self, images, features, proposals, targets=None, ann_type="box", only_gt_proposals=False, **kwargs):
+    def _forward_image(self, features, proposals, targets, classifier_info=(None, None, None)):
+        """One image-labelled batch (DG detic_roi_heads.py:214, :226-234, :320, :341-365): the first WS_NUM_PROPS proposals of every image
+        [+ the image box] (dgx_ws_proposals), three stages WITHOUT matching -- pooler -> box head -> predictor as composed modules, the
+        hand-over dgx_cascade_refine with zero ground truth (its labels are ignored, its valid_out feeds the next stage) -- and
+        image_label_losses per stage.  All lists keep their length, rows carry a validity byte: no device->host read."""
+        import ctypes
+        from ... import _lib as L
+        from ...layers.image_label_ops import label_csr, ws_proposals
+        batch = getattr(proposals, "batch", None)
+        if batch is None or not batch[0].is_cuda:
+            raise RuntimeError("an image-labelled step needs the proposal generator's fixed-length batch tensors on the GPU "
+                               "(ProposalBatch.batch): there is no eager path")
+        for t in targets:
+            if not hasattr(t, "_pos_category_ids"):
+                raise RuntimeError("an image-labelled step needs `pos_category_ids` on every sample (DATALOADER.DATASET_ANN 'image')")
+        boxes, scores, valid = batch
+        B = len(proposals)
+        sizes = [p.image_size for p in proposals]
+        prop, logits, pvalid, Ko = ws_proposals(boxes, scores, valid, sizes, self.ws_num_props, self.add_image_box, self.image_box_size)
+        counts, R, dev = [Ko] * B, B * Ko, prop.device
+        csr = label_csr([t._pos_category_ids for t in targets], dev)
+        row0 = (ctypes.c_int * (B + 1))(*[i * Ko for i in range(B + 1)])
+        gt0 = (ctypes.c_int * (B + 1))(*([0] * (B + 1)))
+        img_h = (ctypes.c_float * B)(*[float(s[0]) for s in sizes])
+        img_w = (ctypes.c_float * B)(*[float(s[1]) for s in sizes])
+        feats = [features[f] for f in self.box_in_features]
+        st = get_event_storage()
+        losses, deltas = {}, None
+        for k in range(self.num_cascade_stages):
+            if k > 0:
+                tr = self.box_predictor[k - 1].box2box_transform
+                d = deltas.detach().contiguous()
+                nb = torch.empty(R, 4, dtype=torch.float32, device=dev)
+                nvalid = torch.empty(R, dtype=torch.uint8, device=dev)
+                gtc = torch.empty(R, dtype=torch.int64, device=dev)
+                gtb = torch.empty(R, 4, dtype=torch.float32, device=dev)
+                nfg = torch.empty(1, dtype=torch.int32, device=dev)
+                L.check(L.lib().dgx_cascade_refine(L.ptr(prop), L.ptr(d), L.ptr(pvalid), B, row0, gt0, img_h, img_w, None, None, None,
+                                                   float(self.cascade_ious[k]), self.num_classes, float(tr.weights[0]), float(tr.weights[1]),
+                                                   float(tr.weights[2]), float(tr.weights[3]), float(tr.scale_clamp), L.ptr(nb), L.ptr(nvalid),
+                                                   L.ptr(gtc), L.ptr(gtb), None, L.ptr(nfg), L.dtype_code(d), L.stream()), "dgx_cascade_refine")
+                prop, pvalid = nb, nvalid
+            x = self.box_pooler.forward_rows(feats, prop, counts, pad_to=256)
+            x = _ScaleGradient.apply(x, 1.0 / self.num_cascade_stages)
+            pred = self.box_predictor[k]
+            sc, deltas = pred(self.box_head[k](x), classifier_info)
+            sc, deltas = sc[:R], deltas[:R]
+            obs = self.__dict__.get("stage_observer")
+            if obs is not None:      # tests: what this stage's image-label loss sees
+                obs(k, dict(boxes=prop, valid=pvalid, scores=sc, counts=counts, image_sizes=sizes))
+            with st.name_scope("stage{}".format(k)):
+                sl = pred.image_label_losses(sc, pvalid, prop, counts, sizes, None, csr=csr)
+            losses.update({n + "_stage{}".format(k): v for n, v in sl.items()})
+        out = ProposalBatch()
+        for i, p in enumerate(proposals):
+            out.append(Instances(p.image_size, proposal_boxes=Boxes(prop[i * Ko:(i + 1) * Ko]), objectness_logits=logits[i * Ko:(i + 1) * Ko]))
+        return out, losses
+
+    def forward(self, images, features, proposals, targets=None, ann_type="box", only_gt_proposals=False,
+                classifier_info=(None, None, None), **kwargs):
         if self.training:
-            assert ann_type == "box", "image-label / caption co-training is outside the shipped configs"
+            if ann_type != "box":
+                if ann_type != "image" or not self.with_image_labels:
+                    raise NotImplementedError("ann_type %r: box batches, and image-labelled batches with WITH_IMAGE_LABELS, are built "
+                                              "(DATALOADER.DATASET_ANN 'box' / 'image')" % (ann_type,))
+                self.__dict__.pop("_before_host_read", None)      # (no sampler, no device->host read to hide work behind)
+                self.__dict__.pop("_gt_batch", None)
+                proposals, losses = self._forward_image(features, proposals, targets, classifier_info)
+                if self.mask_on:        # DG detic_roi_heads.py:329-332: the mask head is not run
+                    losses["loss_mask"] = torch.zeros((1,), device=proposals[0].objectness_logits.device)[0]
+                return proposals, losses
+            if any(c is not None for c in classifier_info):
+                raise NotImplementedError("classifier_info on a box-annotated training step: the fused cascade trains on the built-in "
+                                          "vocabulary (a per-call vocabulary, classifier_info[0], is built for image-labelled steps "
+                                          "and for the predictor called on its own)")
             proposals = self.label_and_sample_proposals(proposals, targets, only_gt_proposals)
             if only_gt_proposals:
                 losses = self._forward_box(features, proposals, targets, only_gt_proposals=True)
@@ -541,6 +621,10 @@ class DeticCascadeROIHeads(nn.Module):
                 params = [q for m in (self.box_head, self.box_predictor) for q in m.parameters() if q.requires_grad]
                 torch.autograd.backward(tot, inputs=list(stop_at) + params)       # (parameters that take their gradient through autograd)
                 losses = {k: v.detach() for k, v in losses.items()}
+            if self.with_image_labels:      # DG detic_roi_heads.py:239-241: every step carries the same key set
+                dev = proposals[0].objectness_logits.device if len(proposals) else "cpu"
+                for k in range(self.num_cascade_stages):
+                    losses["image_loss_stage{}".format(k)] = torch.zeros((), dtype=torch.float32, device=dev)
             if targets[0].has("gt_masks"):
                 losses.update({k: v * self.mask_weight for k, v in self._forward_mask(features, proposals).items()})
             elif self.mask_on:

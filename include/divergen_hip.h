@@ -743,6 +743,53 @@ int dgx_cascade_refine(const float* prop, const void* deltas, const uint8_t* val
                        int64_t* out_cls, float* out_gtb, int64_t* out_src, int32_t* num_fg, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Image-label co-training (WITH_IMAGE_LABELS): an image-labelled batch carries `pos_category_ids` and no boxes.  Every list has
+ * a fixed length with a validity byte per row, so an image step adds no device->host read.  B <= 32; HOST arrays are marked.
+ *
+ * dgx_ws_proposals (detic_roi_heads.py:341-365 `get_top_proposals` + `_add_image_box`): for each image the first
+ * ws_num_props rows with valid != 0 of its proposal list, IN LIST ORDER, each clipped to the image (Boxes.clip); with
+ * add_image_box one more row follows: the centred box of relative size image_box_size (evaluated in double as the reference's
+ * Python does, rounded once) with objectness 1.  A short list is padded with zero rows of valid = 0.  Nothing else is dropped.
+ *   boxes f32 (B,K,4), logits f32 (B,K), valid u8 (B,K) or NULL (all valid); img_h/img_w (host, B);
+ *   out_boxes f32 (B*Ko,4), out_logits f32 (B*Ko), out_valid u8 (B*Ko), Ko = ws_num_props + (add_image_box ? 1 : 0).
+ *
+ * dgx_image_label_loss (detic_fast_rcnn.py:342-434 `image_label_losses`, :524-581): one workgroup per image.
+ *   logits (R, ld_logits) f32|bf16, columns [0, C+1) are read, the others may hold anything; valid u8 (R) or NULL;
+ *   boxes f32 (R,4); row0 (host, B+1) rows of each image, row0[0] = 0, non-decreasing; img_h/img_w (host, B); label_off i32
+ *   (B+1) and labels i32: the positive categories of each image as CSR (a label outside [0, C] selects no row and adds no
+ *   term, but still counts in L_i).
+ *   Row selection per (image, label) over the image's valid rows, ties to the lowest row:
+ *     DGX_IL_MAX_SIZE   arg-max of (x2-x1)*(y2-y1) over all valid rows but the last one; the only row when there is one
+ *     DGX_IL_MAX_SCORE  arg-max of the stored logits[r, label]
+ *     DGX_IL_FIRST      the first valid row         DGX_IL_IMAGE  the last valid row (the image box)
+ *     DGX_IL_MIN_LOSS   arg-min of sum_{c<=C} softplus(s_rc) - s_r,label
+ *   out8 f32 = {image_loss, stats_l_image, pool_stats, stats_select_size, stats_select_x, stats_select_y,
+ *   stats_max_label_score, 0}:  stats_l_image = 1/B sum_images 1/L_i sum_labels [sum_{c<=C} softplus(s_c) - s_label] of the
+ *   selected row (fp32, images and labels in order: bit-reproducible), image_loss = weight * stats_l_image; an image without a
+ *   valid row or without labels contributes 0 and still counts in B; the five statistics are those of the last (image, label)
+ *   that selected a row.  sel_out i32 (label_off[B]): the selected row, relative to the image's first row, or -1.
+ *   dlogits (R, ld_dlogits), dtype of logits, or NULL: when given, EVERY element of the R rows is written (zeros outside the
+ *   selected rows and in columns > C): weight / (B L_i) * upstream[0] * sum over the labels that chose the row of
+ *   (sigmoid(s_c) - [c == label]); upstream f32 (1) device scalar or NULL (= 1).
+ *   sel_in i32 or NULL: when given, the selection and the loss are NOT recomputed (out8, sel_out, ws unused): the launch only
+ *   writes dlogits for these selections -- the backward of a forward that passed dlogits = NULL.
+ *   ws f32: dgx_image_label_workspace_floats(R, B) floats.  R = row0[B] <= 0: out8 = 0, nothing else is touched. */
+#define DGX_IL_MAX_SIZE 0
+#define DGX_IL_MAX_SCORE 1
+#define DGX_IL_FIRST 2
+#define DGX_IL_IMAGE 3
+#define DGX_IL_MIN_LOSS 4
+int dgx_ws_proposals(const float* boxes, const float* logits, const uint8_t* valid, int B, int K, const float* img_h,
+                     const float* img_w, int ws_num_props, int add_image_box, double image_box_size, float* out_boxes,
+                     float* out_logits, uint8_t* out_valid, void* stream);
+int64_t dgx_image_label_workspace_floats(int R, int B);
+int dgx_image_label_loss(const void* logits, int64_t ld_logits, const uint8_t* valid, const float* boxes, int B,
+                         const int* row0, const float* img_h, const float* img_w, const int32_t* label_off,
+                         const int32_t* labels, int C, int mode, float weight, const int32_t* sel_in,
+                         const float* upstream, int32_t* sel_out, float* out8, void* dlogits, int64_t ld_dlogits,
+                         float* ws, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Exact (erf) GELU of the Swin MLP on bf16 activations (swintransformer.py:40-46, nn.GELU()).
  *   dgx_gelu_fwd: y = gelu(x), n elements (n % 8 == 0).
  *   dgx_gelu_bwd_colsum: dx (M, N) = dy * gelu'(x) and, when bias_grad != NULL, bias_grad (N) = beta*bias_grad +

@@ -180,6 +180,8 @@ def do_train(cfg, model, resume=False):
             iteration = iteration + 1
             storage.step()
             optimizer.zero_grad()
+            if cfg.WITH_IMAGE_LABELS:      # ranks may be on different annotation types: the reducer files its ready counts by type
+                reducer.step_kind = data[0].get("ann_type", "box")
             loss_dict = model(data)
             losses = total_loss(loss_dict)
             pending.append((iteration, {k: v.detach() for k, v in loss_dict.items()}))
