@@ -155,6 +155,9 @@ SIGNATURES = {
     "dgx_image_label_workspace_floats": (c_i64, [c_i, c_i]),
     "dgx_image_label_loss": (c_i, [c_p, c_i64, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_i64,
                                    c_p, c_i, c_p]),
+    "dgx_wsddn_workspace_floats": (c_i64, [c_i, c_i, c_i]),
+    "dgx_wsddn_loss": (c_i, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_i64,
+                             c_p, c_i64, c_p, c_i, c_p]),
     "dgx_paste_masks": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p]),
     "dgx_paste_rle": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
     "dgx_rle_encode": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),

@@ -171,6 +171,11 @@ def get_cfg():
     #   method, as the reference does (divergen_amd/csrc/remove_background.hip); without the key the first two are refused at start-up
     #   and RM_BG_PROB is refused with a self-copy method and ignored otherwise.
     cfg.INPUT.SCP_SRC_MODES = False
+    #   MODEL.ROI_BOX_HEAD.WS_PROP_SCORE: admits, with WITH_IMAGE_LABELS, MODEL.ROI_BOX_HEAD.IMAGE_LABEL_LOSS 'wsddn' / 'wsod' (the softmax
+    #   over an image's proposals times the sigmoid class scores: dgx_wsddn_loss, divergen_amd/csrc/wsddn_loss.hip) and the predictor
+    #   branch it reads, MODEL.ROI_BOX_HEAD.WITH_SOFTMAX_PROP (prop_score: Linear-ReLU-Linear, two more GEMMs per cascade stage of an
+    #   image step, parameters that a box step leaves at a zero gradient); without the key both are refused at start-up.
+    cfg.MODEL.ROI_BOX_HEAD.WS_PROP_SCORE = False
     #   SOLVER.ALLREDUCE_DTYPE: "fp32" (the reference's DDP: gradients all-reduced as they are) or "bf16" (gradient buckets go over
     #   xGMI as bf16, half the bytes per step; engine/ddp.py ArenaReducer(wire_dtype=...)).
     cfg.SOLVER.ALLREDUCE_DTYPE = "fp32"

@@ -2,7 +2,8 @@
 reference's recipe is not built is refused by the name of its key, before any data is read or any kernel runs."""
 
 ANN_TYPES = ("box", "image")
-IMAGE_LABEL_LOSSES = ("max_size", "max_score", "first", "image", "min_loss")
+IMAGE_LABEL_LOSSES = ("max_size", "max_score", "first", "image", "min_loss")      # the mode ids DGX_IL_* of the ABI, in this order
+WSDDN_LOSSES = ("wsddn", "wsod")          # the proposal-softmax loss (dgx_wsddn_loss), admitted by MODEL.ROI_BOX_HEAD.WS_PROP_SCORE
 MAX_IMAGES_PER_GPU = 32          # REFINE_MAX_IMAGES of csrc/cascade_refine.hip, IL_MAX_IMAGES of csrc/image_label.hip
 
 
@@ -10,11 +11,16 @@ def _refuse(key, why):
     raise NotImplementedError("%s: %s" % (key, why))
 
 
-def check_image_label_loss(loss, add_image_box, use_sigmoid_ce):
-    """The predictor's own three conditions (its constructor and check_model_keys both come here)."""
-    if loss in ("wsod", "wsddn"):
-        _refuse("MODEL.ROI_BOX_HEAD.IMAGE_LABEL_LOSS %r" % loss, "the WSDDN loss is not built (one of %s)" % (IMAGE_LABEL_LOSSES,))
-    if loss not in IMAGE_LABEL_LOSSES:
+def check_image_label_loss(loss, add_image_box, use_sigmoid_ce, ws_prop_score=False, with_softmax_prop=False):
+    """The predictor's own conditions (its constructor and check_model_keys both come here)."""
+    if loss in WSDDN_LOSSES:
+        if not ws_prop_score:
+            _refuse("MODEL.ROI_BOX_HEAD.IMAGE_LABEL_LOSS %r" % loss, "the WSDDN loss is admitted by MODEL.ROI_BOX_HEAD.WS_PROP_SCORE True only "
+                    "(without the key: one of %s)" % (IMAGE_LABEL_LOSSES,))
+        if not with_softmax_prop:
+            raise ValueError("MODEL.ROI_BOX_HEAD.IMAGE_LABEL_LOSS %r needs MODEL.ROI_BOX_HEAD.WITH_SOFTMAX_PROP True: it reads the "
+                             "proposal-score branch" % loss)
+    elif loss not in IMAGE_LABEL_LOSSES:
         raise ValueError("MODEL.ROI_BOX_HEAD.IMAGE_LABEL_LOSS %r: one of %s" % (loss, IMAGE_LABEL_LOSSES))
     if loss == "image" and not add_image_box:
         raise ValueError("MODEL.ROI_BOX_HEAD.IMAGE_LABEL_LOSS 'image' needs MODEL.ROI_BOX_HEAD.ADD_IMAGE_BOX: it trains on the image box")
@@ -34,12 +40,16 @@ def check_model_keys(cfg):
     if not cfg.WITH_IMAGE_LABELS:
         return
     h = cfg.MODEL.ROI_BOX_HEAD
-    check_image_label_loss(h.IMAGE_LABEL_LOSS, h.ADD_IMAGE_BOX, h.USE_SIGMOID_CE)
-    for key, on in (("MODEL.ROI_BOX_HEAD.WITH_SOFTMAX_PROP", h.WITH_SOFTMAX_PROP), ("MODEL.ROI_BOX_HEAD.SOFTMAX_WEAK_LOSS", h.SOFTMAX_WEAK_LOSS),
+    ws_prop = bool(h.get("WS_PROP_SCORE", False))
+    check_image_label_loss(h.IMAGE_LABEL_LOSS, h.ADD_IMAGE_BOX, h.USE_SIGMOID_CE, ws_prop, h.WITH_SOFTMAX_PROP)
+    if h.WITH_SOFTMAX_PROP and not ws_prop:
+        _refuse("MODEL.ROI_BOX_HEAD.WITH_SOFTMAX_PROP", "the proposal-score branch is admitted by MODEL.ROI_BOX_HEAD.WS_PROP_SCORE True only")
+    for key, on in (("MODEL.ROI_BOX_HEAD.SOFTMAX_WEAK_LOSS", h.SOFTMAX_WEAK_LOSS),
                     ("MODEL.ROI_BOX_HEAD.ADD_FEATURE_TO_PROP", h.ADD_FEATURE_TO_PROP), ("MODEL.WITH_CAPTION", cfg.MODEL.WITH_CAPTION),
                     ("MODEL.DYNAMIC_CLASSIFIER", cfg.MODEL.DYNAMIC_CLASSIFIER)):
         if on:
-            _refuse(key, "not built: image-label co-training covers the five row-selection losses on the sigmoid classifier only")
+            _refuse(key, "not built: image-label co-training covers the five row-selection losses and, with MODEL.ROI_BOX_HEAD.WS_PROP_SCORE, "
+                    "the WSDDN loss, on the sigmoid classifier only")
     method = cfg.INPUT.USE_COPY_METHOD
     if method in ("self_copy", "both") or str(method).startswith("p:"):
         _refuse("INPUT.USE_COPY_METHOD %r" % method, "self copy-paste draws a second BOX-annotated image; with WITH_IMAGE_LABELS the training set "

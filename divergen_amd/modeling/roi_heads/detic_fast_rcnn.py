@@ -167,12 +167,17 @@ class DeticFastRCNNOutputLayers(nn.Module):
                  loss_weight=1.0, mult_proposal_score=False, use_sigmoid_ce=False, use_fed_loss=False,
                  ignore_zero_cats=False, fed_loss_num_cat=50, prior_prob=0.01, cat_freq_path="",
                  fed_loss_freq_weight=0.5, use_zeroshot_cls=False, cls_score=None, divergen_box_loss=True, only_paste_sup=False,
-                 image_label_loss="", image_loss_weight=0.1, add_image_box=False, **unused):
+                 image_label_loss="", image_loss_weight=0.1, add_image_box=False, with_softmax_prop=False, ws_prop_score=False,
+                 **unused):
         super().__init__()
         # WITH_IMAGE_LABELS (DG detic_fast_rcnn.py:342-434): "" = the predictor trains on box annotations only
+        from ...config.image_labels import WSDDN_LOSSES, check_image_label_loss
         if image_label_loss:
-            from ...config.image_labels import check_image_label_loss
-            check_image_label_loss(image_label_loss, add_image_box, use_sigmoid_ce)
+            check_image_label_loss(image_label_loss, add_image_box, use_sigmoid_ce, ws_prop_score, with_softmax_prop)
+        if with_softmax_prop and not ws_prop_score:
+            raise NotImplementedError("MODEL.ROI_BOX_HEAD.WITH_SOFTMAX_PROP: the proposal-score branch is admitted by "
+                                      "MODEL.ROI_BOX_HEAD.WS_PROP_SCORE True only")
+        self.with_softmax_prop, self.wsddn = with_softmax_prop, image_label_loss in WSDDN_LOSSES
         self.image_label_loss, self.image_loss_weight, self.add_image_box = image_label_loss, float(image_loss_weight), add_image_box
         if box_reg_loss_type != "smooth_l1":
             raise NotImplementedError("MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE %r: only 'smooth_l1' is built (the shipped configs)"
@@ -200,6 +205,13 @@ class DeticFastRCNNOutputLayers(nn.Module):
             nn.init.normal_(self.bbox_pred.weight, std=0.001)
             for l in (self.cls_score, self.bbox_pred):
                 nn.init.constant_(l.bias, 0)
+        if with_softmax_prop:
+            # DG detic_fast_rcnn.py:120-128: the proposal-score branch of the WSDDN loss.  Evaluated only where something reads it (a
+            # training image step with IMAGE_LABEL_LOSS 'wsddn'): the reference computes it everywhere and drops it
+            self.prop_score = nn.Sequential(Linear(input_size, input_size), nn.ReLU(), Linear(input_size, num_classes + 1))
+            c2_xavier_fill(self.prop_score[0])
+            nn.init.normal_(self.prop_score[-1].weight, mean=0, std=0.001)
+            nn.init.constant_(self.prop_score[-1].bias, 0)
         self.box2box_transform, self.smooth_l1_beta = box2box_transform, smooth_l1_beta
         self.test_score_thresh, self.test_nms_thresh, self.test_topk_per_image = test_score_thresh, test_nms_thresh, test_topk_per_image
         self.mult_proposal_score, self.use_sigmoid_ce, self.use_fed_loss = mult_proposal_score, use_sigmoid_ce, use_fed_loss
@@ -222,12 +234,14 @@ class DeticFastRCNNOutputLayers(nn.Module):
         h = cfg.MODEL.ROI_BOX_HEAD
         from ...config.image_labels import check_model_keys
         check_model_keys(cfg)
+        ws_prop = bool(h.get("WS_PROP_SCORE", False))
         if h.USE_ZEROSHOT_CLS:
-            for key, on in (("MODEL.ROI_BOX_HEAD.WITH_SOFTMAX_PROP", h.WITH_SOFTMAX_PROP), ("MODEL.DYNAMIC_CLASSIFIER", cfg.MODEL.DYNAMIC_CLASSIFIER),
+            for key, on in (("MODEL.ROI_BOX_HEAD.WITH_SOFTMAX_PROP", h.WITH_SOFTMAX_PROP and not ws_prop), ("MODEL.DYNAMIC_CLASSIFIER", cfg.MODEL.DYNAMIC_CLASSIFIER),
                             ("MODEL.WITH_CAPTION", cfg.MODEL.WITH_CAPTION)):
                 if on:
                     raise NotImplementedError("%s is not built: the open-vocabulary classifier trains on box annotations and image labels "
-                                              "(no proposal-score branch, dynamic classifier or caption losses)" % key)
+                                              "(no dynamic classifier or caption losses; the proposal-score branch with "
+                                              "MODEL.ROI_BOX_HEAD.WS_PROP_SCORE True only)" % key)
         return dict(input_shape=input_shape, cls_score=ZeroShotClassifier(cfg, input_shape) if h.USE_ZEROSHOT_CLS else None,
                     box2box_transform=box2box_transform or Box2BoxTransform(weights=h.BBOX_REG_WEIGHTS),
                     num_classes=cfg.MODEL.ROI_HEADS.NUM_CLASSES, cls_agnostic_bbox_reg=h.CLS_AGNOSTIC_BBOX_REG,
@@ -240,23 +254,36 @@ class DeticFastRCNNOutputLayers(nn.Module):
                     divergen_box_loss=cfg.MODEL.USE_DIVERGEN_BOX_LOSS and cfg.MODEL.get("USE_XPASTE_BOX_LOSS", True),
                     only_paste_sup=cfg.MODEL.get("ONLY_PASTE_SUP", False),
                     image_label_loss=h.IMAGE_LABEL_LOSS if cfg.WITH_IMAGE_LABELS else "", image_loss_weight=h.IMAGE_LOSS_WEIGHT,
-                    add_image_box=h.ADD_IMAGE_BOX)
+                    add_image_box=h.ADD_IMAGE_BOX, with_softmax_prop=bool(h.WITH_SOFTMAX_PROP) and ws_prop, ws_prop_score=ws_prop)
 
-    def forward(self, x, classifier_info=(None, None, None)):
+    def forward(self, x, classifier_info=(None, None, None), with_prop_scores=False):
         if x.dim() > 2:
             x = torch.flatten(x, start_dim=1)
         if classifier_info[2] is not None:
             raise NotImplementedError("caption scores (classifier_info[2], MODEL.WITH_CAPTION) are not built: the box predictor "
                                       "trains on box annotations only")
+        # DG :462-464 returns the proposal scores from every call and every caller but the WSDDN loss drops them: here they are computed
+        # only for that reader, which asks for them (`with_prop_scores`: the image step under 'wsddn')
+        if with_prop_scores and not self.with_softmax_prop:
+            raise RuntimeError("with_prop_scores on a predictor built without MODEL.ROI_BOX_HEAD.WITH_SOFTMAX_PROP")
+        prop = (self.prop_score_rows(x),) if with_prop_scores else ()
         if self.use_zeroshot_cls:
-            return self.cls_score(x, classifier=classifier_info[0]), self._bbox_pred_rows(x)
+            return (self.cls_score(x, classifier=classifier_info[0]), self._bbox_pred_rows(x)) + prop
         if classifier_info[0] is not None:
             raise NotImplementedError("a per-call vocabulary (classifier_info[0]) needs MODEL.ROI_BOX_HEAD.USE_ZEROSHOT_CLS")
         y = self.forward_joint(x)
         if y is not None:
             c1, nb = self.cls_score.out_features, self.bbox_pred.out_features
-            return y[:, :c1], y[:, c1:c1 + nb]
-        return self.cls_score(x), self.bbox_pred(x)
+            return (y[:, :c1], y[:, c1:c1 + nb]) + prop
+        return (self.cls_score(x), self.bbox_pred(x)) + prop
+
+    def prop_score_rows(self, x):
+        """prop_score(x) as the column slice [:, :C+1] of the second GEMM's own (R, ceil8(C+1)) output: the pad columns are zeros (zero
+        weight rows, zero bias padding) and the loss kernel reads 16-byte rows."""
+        p = self.prop_score
+        if not x.is_cuda:
+            return F.linear(F.relu(F.linear(x, p[0].weight, p[0].bias)), p[2].weight, p[2].bias)
+        return linear_padded(p[1](p[0](x)), p[2].weight, p[2].bias)[:, :p[2].out_features]
 
     def forward_joint(self, x):
         """(R, pad8(C + 1 + 4)) logits | box deltas | zero columns from ONE GEMM over the arena group, or None when the parameters
@@ -363,16 +390,26 @@ class DeticFastRCNNOutputLayers(nn.Module):
             losses["loss_paste_ins"], losses["loss_nopaste_ins"] = self.paste_split(scores, gt_classes, w, paste_src)
         return losses
 
-    def image_label_losses(self, scores, valid, boxes, counts, image_sizes, image_labels, csr=None):
+    def image_label_losses(self, scores, valid, boxes, counts, image_sizes, image_labels, csr=None, prop_scores=None):
         """DG detic_fast_rcnn.py:342-434 for one cascade stage of an image-labelled batch: one launch selects a row per (image, label),
         sums the sigmoid BCE of the selected rows and leaves the logged statistics on the device (dgx_image_label_loss); loss_cls and
         loss_box_reg are the reference's exact zeros.  scores (R, C+1) may be the strided column slice of the joint predictor output."""
-        from ...layers.image_label_ops import image_label_loss
+        from ...layers.image_label_ops import image_label_loss, wsddn_loss
         if not self.image_label_loss:
             raise RuntimeError("image_label_losses on a predictor built without WITH_IMAGE_LABELS")
+        if self.wsddn and prop_scores is None:      # DG :510 `assert prop_score is not None`
+            raise RuntimeError("IMAGE_LABEL_LOSS %r needs the proposal scores (predictions[2], WITH_SOFTMAX_PROP)" % self.image_label_loss)
         with torch.autocast("cuda", enabled=False):
-            loss, out, _ = image_label_loss(scores, valid, boxes, counts, image_sizes, image_labels, self.image_label_loss,
-                                            self.image_loss_weight, csr=csr)
+            if self.wsddn:
+                if prop_scores.dtype != scores.dtype:
+                    # the open-vocabulary classifier scores in fp32, the GEMM branch in bf16; the kernel reads one dtype: the proposal scores
+                    # are widened (one elementwise copy of (R, C+1) per stage on that predictor; the Linear predictor has bf16 for both)
+                    prop_scores = prop_scores.to(scores.dtype)
+                # DG :509-521: softmax over the image's proposals x sigmoid class scores, BCE of the clamped per-class sums (dgx_wsddn_loss)
+                loss, out, _ = wsddn_loss(scores, prop_scores, valid, boxes, counts, image_sizes, image_labels, self.image_loss_weight, csr=csr)
+            else:
+                loss, out, _ = image_label_loss(scores, valid, boxes, counts, image_sizes, image_labels, self.image_label_loss,
+                                                self.image_loss_weight, csr=csr)
         st = get_event_storage()
         from ...utils.events import DeferredScalar
         st.put_scalar("stats_l_image", DeferredScalar(lambda o: o[1], out))

@@ -575,13 +575,14 @@ class DeticCascadeROIHeads(nn.Module):
             x = self.box_pooler.forward_rows(feats, prop, counts, pad_to=256)
             x = _ScaleGradient.apply(x, 1.0 / self.num_cascade_stages)
             pred = self.box_predictor[k]
-            sc, deltas = pred(self.box_head[k](x), classifier_info)
-            sc, deltas = sc[:R], deltas[:R]
+            out = pred(self.box_head[k](x), classifier_info, with_prop_scores=pred.wsddn)      # (the WSDDN loss reads predictions[2]; nothing else does)
+            sc, deltas = out[0][:R], out[1][:R]
+            ps = out[2][:R] if len(out) > 2 else None
             obs = self.__dict__.get("stage_observer")
             if obs is not None:      # tests: what this stage's image-label loss sees
-                obs(k, dict(boxes=prop, valid=pvalid, scores=sc, counts=counts, image_sizes=sizes))
+                obs(k, dict(boxes=prop, valid=pvalid, scores=sc, prop_scores=ps, counts=counts, image_sizes=sizes))
             with st.name_scope("stage{}".format(k)):
-                sl = pred.image_label_losses(sc, pvalid, prop, counts, sizes, None, csr=csr)
+                sl = pred.image_label_losses(sc, pvalid, prop, counts, sizes, None, csr=csr, prop_scores=ps)
             losses.update({n + "_stage{}".format(k): v for n, v in sl.items()})
         out = ProposalBatch()
         for i, p in enumerate(proposals):

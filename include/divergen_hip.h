@@ -790,6 +790,39 @@ int dgx_image_label_loss(const void* logits, int64_t ld_logits, const uint8_t* v
                          float* ws, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * dgx_wsddn_loss (detic_fast_rcnn.py:509-521 `_wsddn_loss` inside :342-434 `image_label_losses`): the image-label loss that
+ * selects no row.  Grid over (image, block of 64 columns); conventions of dgx_image_label_loss: B <= 32, HOST arrays row0 / img_h /
+ * img_w, label CSR on the device, a validity byte per row.
+ *   logits, prop (R, ld_*) f32|bf16 (one dtype), columns [0, C] are read, the others may hold anything (NaN included).
+ *   Per image i with valid rows V_i and labels l_1..l_L (duplicates kept, list order):
+ *     p_rc = softmax over r in V_i of prop[r,c], per column c = 0..C;   S_c = sum_r sigmoid(logits[r,c]) p_rc   (fp32)
+ *     Sc_c = clamp(S_c, 1e-10f, 1.0f) -- the reference clamps an fp32 tensor to [1e-10, 1 - 1e-10], whose upper bound rounds to 1.0f
+ *     per label: 1/(C+1) sum_c BCE(Sc_c, [c == l]), BCE = torch's binary_cross_entropy (logs clamped below at -100), computed as
+ *     the all-negative column sum of the image corrected in column l;  image term 1/L sum over labels;
+ *     stats_l_image = 1/B sum over images, image_loss = weight * stats_l_image.  An image without valid rows or without labels
+ *     contributes 0 and still counts in B; a label outside [0, C] adds no term and still counts in L.
+ *   sel_out i32 (label_off[B]): arg-max over valid rows of sigmoid(logits[r,l]) p_rl, ties to the lowest row, -1 when there is none.
+ *   out8 as dgx_image_label_loss: {image_loss, stats_l_image, pool_stats, stats_select_size, stats_select_x, stats_select_y,
+ *   stats_max_label_score, 0}, the five statistics from the row in sel_out of the last (image, label) that has one.
+ *   Gradients (both or neither; dtype of the inputs; EVERY element of the R rows written, exact zeros in invalid rows and in
+ *   columns > C), with K = weight / (B L (C+1)) * upstream[0] (upstream f32 (1) device scalar or NULL = 1) and
+ *   G_c = sum over labels of (Sc_c - [c == l]) / max((1 - Sc_c) Sc_c, 1e-12) where 1e-10f <= S_c <= 1.0f, else 0:
+ *     dlogits[r,c] = K G_c p_rc sigma_rc (1 - sigma_rc),   dprop[r,c] = K G_c p_rc (sigma_rc - S_c),
+ *   sigma and S rounded to fp32 before 1 - sigma and 1 - S are formed, as in torch's backward formulas.
+ *   Forward launch (dlogits = dprop = NULL, col_stats_in = NULL): loss, sel_out, out8; leaves in ws, first, the column statistics
+ *   (B, 3, C+1) = {column maximum, softmax denominator, unclamped S_c}.  Gradient launch (col_stats_in = those statistics): one
+ *   pass over the two inputs writes both gradients; out8, sel_out, ws unused.  Gradient buffers without col_stats_in: both.
+ *   No floating-point atomics, every sum in a fixed order: two runs give the same bits.  Nothing goes back to the host.
+ *   ws f32: dgx_wsddn_workspace_floats(R, B, C) floats.  R = row0[B] <= 0: out8 = 0 and NOTHING else is written -- sel_out too
+ *   (the label count lives on the device): a caller that reads sel_out after such a call fills it with -1 beforehand. */
+int64_t dgx_wsddn_workspace_floats(int R, int B, int C);
+int dgx_wsddn_loss(const void* logits, int64_t ld_logits, const void* prop, int64_t ld_prop, const uint8_t* valid,
+                   const float* boxes, int B, const int* row0, const float* img_h, const float* img_w,
+                   const int32_t* label_off, const int32_t* labels, int C, float weight, const float* col_stats_in,
+                   const float* upstream, int32_t* sel_out, float* out8, void* dlogits, int64_t ld_dlogits, void* dprop,
+                   int64_t ld_dprop, float* ws, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Exact (erf) GELU of the Swin MLP on bf16 activations (swintransformer.py:40-46, nn.GELU()).
  *   dgx_gelu_fwd: y = gelu(x), n elements (n % 8 == 0).
  *   dgx_gelu_bwd_colsum: dx (M, N) = dy * gelu'(x) and, when bias_grad != NULL, bias_grad (N) = beta*bias_grad +

@@ -2,6 +2,10 @@
 Swin size / resolution / batch on the command line:
 
     python tools/image_label_bench.py [--size T] [--res 640] [--batch 4] [--steps 10] [--loss max_size]
+
+--loss wsddn (alias wsod) turns on MODEL.ROI_BOX_HEAD.WS_PROP_SCORE and WITH_SOFTMAX_PROP and also reports, from one profiled image step,
+the device time of the three dgx_wsddn_loss launches per cascade stage next to the bytes they must move (two reads and two writes of
+R x (C+1) bf16 elements per stage).
 """
 import argparse
 import json
@@ -34,6 +38,9 @@ def main():
     cfg.merge_from_list(["MODEL.SWIN.SIZE", a.size, "WITH_IMAGE_LABELS", True, "MODEL.ROI_BOX_HEAD.IMAGE_LABEL_LOSS", a.loss,
                          "MODEL.ROI_BOX_HEAD.ADD_IMAGE_BOX", True,
                          "MODEL.ROI_BOX_HEAD.CAT_FREQ_PATH", os.path.join(ROOT, "configs", "metadata", "lvis_v1_train_cat_info.json")])
+    wsddn = a.loss in ("wsddn", "wsod")
+    if wsddn:
+        cfg.merge_from_list(["MODEL.ROI_BOX_HEAD.WS_PROP_SCORE", True, "MODEL.ROI_BOX_HEAD.WITH_SOFTMAX_PROP", True])
     torch.manual_seed(0)
     model = build_model(cfg).train()
     opt = build_optimizer(cfg, model)
@@ -66,6 +73,23 @@ def main():
             e1.record()
             torch.cuda.synchronize()
             out["ms_per_%s_step" % name] = round(e0.elapsed_time(e1) / a.steps, 3)
+        if wsddn:
+            from torch.profiler import ProfilerActivity, profile
+            with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                step(img)
+                torch.cuda.synchronize()
+            us = {}
+            for ev in prof.events():
+                for k in ("wsddn_stats_kernel", "wsddn_fold_kernel", "wsddn_grad_kernel"):
+                    if k in ev.name:
+                        us[k] = us.get(k, 0.0) + ev.device_time_total
+            stages = len(model.roi_heads.box_predictor)
+            R = a.batch * (cfg.MODEL.ROI_BOX_HEAD.WS_NUM_PROPS + 1)
+            nbytes = 4 * R * (C + 1) * 2
+            out["wsddn_us_per_stage"] = {k: round(v / stages, 2) for k, v in us.items()}
+            out["wsddn_bytes_per_stage"] = nbytes
+            if us:
+                out["wsddn_gb_per_s"] = round(nbytes / (sum(us.values()) / stages * 1e-6) / 1e9, 1)
     print(json.dumps(out))
 
 
