@@ -171,6 +171,10 @@ SIGNATURES = {
     "dgx_detic_losses_strided": (c_i, [c_p, c_i64, c_p, c_i64] + [c_p] * 5 + [c_i, c_i, c_f, c_f, c_f, c_f, c_p, c_i64, c_i, c_p, c_p, c_p, c_i, c_p]),
     "dgx_detic_grad_scale": (c_i, [c_p, c_i64, c_i, c_i, c_p, c_p, c_p, c_i, c_p]),
     "dgx_fed_class_mask": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p]),
+    "dgx_dyn_class_sample": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "dgx_zs_gather": (c_i, [c_p, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p]),
+    "dgx_remap_labels": (c_i, [c_p, c_i64, c_p, c_i, c_p, c_p]),
+    "dgx_zs_logits_f32": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_i64, c_p]),
     "dgx_gelu_fwd": (c_i, [c_p, c_p, c_i64, c_p]),
     "dgx_gelu_bwd_workspace_bytes": (c_i64, [c_i, c_i]),
     "dgx_gelu_bwd_colsum": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_p, c_p]),

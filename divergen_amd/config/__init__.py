@@ -176,6 +176,12 @@ def get_cfg():
     #   branch it reads, MODEL.ROI_BOX_HEAD.WITH_SOFTMAX_PROP (prop_score: Linear-ReLU-Linear, two more GEMMs per cascade stage of an
     #   image step, parameters that a box step leaves at a zero gradient); without the key both are refused at start-up.
     cfg.MODEL.ROI_BOX_HEAD.WS_PROP_SCORE = False
+    #   MODEL.DYNAMIC_VOCAB: admits MODEL.DYNAMIC_CLASSIFIER True with MODEL.NUM_SAMPLE_CATS (a vocabulary sampled per batch: the classes
+    #   present plus frequency-weighted negatives; the classifier, its logits and the losses are NUM_SAMPLE_CATS + 1 columns wide), on
+    #   the open-vocabulary classifier (MODEL.ROI_BOX_HEAD.USE_ZEROSHOT_CLS), with or without WITH_IMAGE_LABELS: four kernels
+    #   (dgx_dyn_class_sample, dgx_zs_gather, dgx_remap_labels, dgx_zs_logits_f32; divergen_amd/csrc/dyn_vocab.hip, config/dynamic_vocab.py).  Without the
+    #   key DYNAMIC_CLASSIFIER is refused at start-up.
+    cfg.MODEL.DYNAMIC_VOCAB = False
     #   SOLVER.ALLREDUCE_DTYPE: "fp32" (the reference's DDP: gradients all-reduced as they are) or "bf16" (gradient buckets go over
     #   xGMI as bf16, half the bytes per step; engine/ddp.py ArenaReducer(wire_dtype=...)).
     cfg.SOLVER.ALLREDUCE_DTYPE = "fp32"

@@ -46,7 +46,7 @@ def check_model_keys(cfg):
         _refuse("MODEL.ROI_BOX_HEAD.WITH_SOFTMAX_PROP", "the proposal-score branch is admitted by MODEL.ROI_BOX_HEAD.WS_PROP_SCORE True only")
     for key, on in (("MODEL.ROI_BOX_HEAD.SOFTMAX_WEAK_LOSS", h.SOFTMAX_WEAK_LOSS),
                     ("MODEL.ROI_BOX_HEAD.ADD_FEATURE_TO_PROP", h.ADD_FEATURE_TO_PROP), ("MODEL.WITH_CAPTION", cfg.MODEL.WITH_CAPTION),
-                    ("MODEL.DYNAMIC_CLASSIFIER", cfg.MODEL.DYNAMIC_CLASSIFIER)):
+                    ("MODEL.DYNAMIC_CLASSIFIER", cfg.MODEL.DYNAMIC_CLASSIFIER and not cfg.MODEL.get("DYNAMIC_VOCAB", False))):
         if on:
             _refuse(key, "not built: image-label co-training covers the five row-selection losses and, with MODEL.ROI_BOX_HEAD.WS_PROP_SCORE, "
                     "the WSDDN loss, on the sigmoid classifier only")

@@ -102,9 +102,17 @@ class EarlyLosses(dict):
 class CustomRCNN(nn.Module):
     @configurable
     def __init__(self, *, backbone, proposal_generator, roi_heads, pixel_mean, pixel_std, input_format=None,
-                 vis_period=0, fp16=False, with_image_labels=False, roi_head_name="", dataset_loss_weight=(), **unused):
+                 vis_period=0, fp16=False, with_image_labels=False, roi_head_name="", dataset_loss_weight=(),
+                 dynamic_classifier=False, num_sample_cats=50, num_classes=None, freq_weight=None, **unused):
         super().__init__()
         assert proposal_generator is not None
+        # MODEL.DYNAMIC_CLASSIFIER (custom_rcnn.py:50-55): a vocabulary of num_sample_cats classes sampled per batch.  freq_weight is a
+        # plain attribute, as in the reference: the state dict does not change
+        self.dynamic_classifier = bool(dynamic_classifier)
+        if self.dynamic_classifier:
+            if num_classes is None or freq_weight is None:
+                raise ValueError("dynamic_classifier needs num_classes and freq_weight")
+            self.freq_weight, self.num_classes, self.num_sample_cats = freq_weight, int(num_classes), int(num_sample_cats)
         # WITH_IMAGE_LABELS: every sample carries `ann_type` ('box' | 'image') and `pos_category_ids`, a batch holds one type
         self.with_image_labels = bool(with_image_labels)
         self.dataset_loss_weight = [float(w) for w in dataset_loss_weight]      # MODEL.DATASET_LOSS_WEIGHT, by `dataset_source`
@@ -129,9 +137,16 @@ class CustomRCNN(nn.Module):
 
     @classmethod
     def from_config(cls, cfg):
+        from ...config.dynamic_vocab import check_dynamic_vocab
+        check_dynamic_vocab(cfg)
+        dyn = {}
+        if cfg.MODEL.DYNAMIC_CLASSIFIER and cfg.MODEL.get("DYNAMIC_VOCAB", False):        # (custom_rcnn.py:78-83)
+            from ..roi_heads.detic_fast_rcnn import load_class_freq
+            dyn = dict(dynamic_classifier=True, num_classes=cfg.MODEL.ROI_HEADS.NUM_CLASSES, num_sample_cats=cfg.MODEL.NUM_SAMPLE_CATS,
+                       freq_weight=load_class_freq(cfg.MODEL.ROI_BOX_HEAD.CAT_FREQ_PATH, cfg.MODEL.ROI_BOX_HEAD.FED_LOSS_FREQ_WEIGHT))
         backbone = build_backbone(cfg)
         shape = backbone.output_shape()
-        return dict(backbone=backbone, proposal_generator=build_proposal_generator(cfg, shape),
+        return dict(**dyn, backbone=backbone, proposal_generator=build_proposal_generator(cfg, shape),
                     roi_heads=build_roi_heads(cfg, shape), input_format=cfg.INPUT.FORMAT, vis_period=cfg.VIS_PERIOD,
                     pixel_mean=cfg.MODEL.PIXEL_MEAN, pixel_std=cfg.MODEL.PIXEL_STD, fp16=cfg.FP16,
                     with_image_labels=cfg.WITH_IMAGE_LABELS, roi_head_name=cfg.MODEL.ROI_HEADS.NAME,
@@ -209,14 +224,46 @@ class CustomRCNN(nn.Module):
             losses[k] = losses[k] * w
         return losses
 
-    def _image_step_losses(self, images, features, gt_instances):
+    def _sample_cls_inds(self, gt_instances, ann_type="box", gt_classes=None):
+        """custom_rcnn.py:226-247 without a device->host read: one exponential_ draw of C + 1 values (what the reference's multinomial
+        draws at this position of torch's random stream; it draws only when fewer than num_sample_cats classes appear, see below) and
+        dgx_dyn_class_sample.  Box step: the
+        concatenated gt_classes, weighted by freq_weight over its len(freq_weight) classes; image step: the images' pos_category_ids,
+        uniform over num_classes -- there the column count is known from the lists."""
+        from ...layers.dyn_vocab_ops import DynamicVocab, sample_classes, sampling_weights
+        from ...utils.h2d import upload_i32
+        dev = self.device
+        n_host = None
+        if ann_type == "box":
+            if gt_classes is None:
+                gt_classes = torch.cat([x.gt_classes for x in gt_instances]) if len(gt_instances) else torch.zeros(0, dtype=torch.int64, device=dev)
+            C, weight = len(self.freq_weight), self.freq_weight
+        else:
+            flat = [int(c) for x in gt_instances for c in x._pos_category_ids]
+            if flat and (max(flat) >= self.num_classes or min(flat) < 0):
+                raise ValueError("pos_category_ids outside [0, %d)" % self.num_classes)       # (the reference's assert, :240)
+            gt_classes = upload_i32(flat, dev).long() if flat else torch.zeros(0, dtype=torch.int64, device=dev)
+            C, weight = self.num_classes, None
+            n_host = max(min(self.num_sample_cats, C), len(set(flat)))
+        prob0 = sampling_weights(weight, C, dev)
+        if ann_type != "box" and len(set(flat)) >= self.num_sample_cats:
+            expo = prob0        # nothing is drawn and the host knows it: no draw from the generator either, as in the reference (utils.py:20)
+        else:
+            # a box step draws on EVERY step -- the number of distinct classes is on the device -- where the reference's multinomial
+            # draws only when fewer than num_sample_cats appear: on the other steps torch's random stream runs C + 1 values ahead of it
+            expo = torch.empty_like(prob0).exponential_(1)
+        inds, cls_id_map, n = sample_classes(gt_classes, prob0, expo, C, self.num_classes, self.num_sample_cats)
+        return DynamicVocab(inds, cls_id_map, n_host if (n_host is not None and torch.is_tensor(n)) else n, self.num_classes)
+
+    def _image_step_losses(self, images, features, gt_instances, classifier_info=(None, None, None)):
         """An image-labelled batch (custom_rcnn.py:166-194): the proposal generator runs for its proposals only, without gradient
         tracking (no autograd graph is built or held) -- its losses are reported as exact zeros (the reference's `v * 0` of finite
         values), so neither its backward nor the early backward pass exist in this step; the RoI heads train the cascade's
         classifiers on the image labels."""
         with torch.no_grad():
             proposals, proposal_losses = self.proposal_generator(images, features, gt_instances)
-        proposals, detector_losses = self.roi_heads(images, features, proposals, gt_instances, ann_type="image")
+        proposals, detector_losses = self.roi_heads(images, features, proposals, gt_instances, ann_type="image",
+                                                    classifier_info=classifier_info)
         losses = dict(detector_losses)
         losses.update({k: v.detach().float().reshape(()) * 0.0 for k, v in proposal_losses.items()})
         return proposals, losses
@@ -237,7 +284,8 @@ class CustomRCNN(nn.Module):
             with torch.autocast("cuda", dtype=torch.bfloat16):
                 if grads_on:
                     fg, features = _shared_gradient_maps(features)
-                proposals, losses = self._image_step_losses(images, features, gt_instances)
+                ci = (None, self._sample_cls_inds(gt_instances, "image"), None) if self.dynamic_classifier else (None, None, None)
+                proposals, losses = self._image_step_losses(images, features, gt_instances, ci)
             losses = self._weight_by_source(batched_inputs, losses)
             return (proposals, losses) if self.return_proposal else losses
         with torch.autocast("cuda", dtype=torch.bfloat16):
@@ -246,6 +294,14 @@ class CustomRCNN(nn.Module):
                 fg, joined = _shared_gradient_maps(features)
             if hasattr(self.roi_heads, "prepare_targets") and not only_gt_proposals:
                 self.roi_heads.prepare_targets(gt_instances)
+            ci = {}
+            if self.dynamic_classifier:
+                if only_gt_proposals:
+                    raise NotImplementedError("MODEL.DYNAMIC_CLASSIFIER with only_gt_proposals (BSGAL's held-out pass)")
+                # after the backbone, before the proposal generator: the reference's position in torch's random stream (:159-166)
+                pre = self.roi_heads.__dict__.get("_gt_batch")
+                cat = pre[2] if (pre is not None and pre[0] is gt_instances and sum(len(t) for t in gt_instances)) else None
+                ci = dict(classifier_info=(None, self._sample_cls_inds(gt_instances, "box", cat), None))
             if early and grads_on:
                 prev = self.__dict__.get("_early_outstanding")
                 if prev is not None and not prev.consumed:
@@ -268,7 +324,7 @@ class CustomRCNN(nn.Module):
                     self.roi_heads.__dict__["_early_box_backward"] = list(stops)
                 try:
                     proposals, detector_losses = self.roi_heads(images, joined, proposals, gt_instances, ann_type="box",
-                                                                only_gt_proposals=only_gt_proposals)
+                                                                only_gt_proposals=only_gt_proposals, **ci)
                 finally:
                     pending = self.roi_heads.__dict__.pop("_before_host_read", None)
                     self.roi_heads.__dict__.pop("_early_box_backward", None)
@@ -280,7 +336,7 @@ class CustomRCNN(nn.Module):
                     features = joined
                 proposals, proposal_losses = self.proposal_generator(images, features, gt_instances)
                 proposals, detector_losses = self.roi_heads(images, features, proposals, gt_instances, ann_type="box",
-                                                            only_gt_proposals=only_gt_proposals)
+                                                            only_gt_proposals=only_gt_proposals, **ci)
         losses = EarlyLosses() if (early and grads_on) else {}
         losses.update(detector_losses)
         losses.update(proposal_losses)

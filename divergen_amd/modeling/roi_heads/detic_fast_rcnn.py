@@ -235,8 +235,13 @@ class DeticFastRCNNOutputLayers(nn.Module):
         from ...config.image_labels import check_model_keys
         check_model_keys(cfg)
         ws_prop = bool(h.get("WS_PROP_SCORE", False))
+        dyn_vocab = bool(cfg.MODEL.get("DYNAMIC_VOCAB", False))
+        if dyn_vocab:
+            from ...config.dynamic_vocab import check_dynamic_vocab
+            check_dynamic_vocab(cfg)
         if h.USE_ZEROSHOT_CLS:
-            for key, on in (("MODEL.ROI_BOX_HEAD.WITH_SOFTMAX_PROP", h.WITH_SOFTMAX_PROP and not ws_prop), ("MODEL.DYNAMIC_CLASSIFIER", cfg.MODEL.DYNAMIC_CLASSIFIER),
+            for key, on in (("MODEL.ROI_BOX_HEAD.WITH_SOFTMAX_PROP", h.WITH_SOFTMAX_PROP and not ws_prop),
+                            ("MODEL.DYNAMIC_CLASSIFIER", cfg.MODEL.DYNAMIC_CLASSIFIER and not dyn_vocab),
                             ("MODEL.WITH_CAPTION", cfg.MODEL.WITH_CAPTION)):
                 if on:
                     raise NotImplementedError("%s is not built: the open-vocabulary classifier trains on box annotations and image labels "
@@ -317,9 +322,11 @@ class DeticFastRCNNOutputLayers(nn.Module):
         return (_FUSED_LOSSES and scores.is_cuda and scores.shape[0] > 0 and self.use_sigmoid_ce and deltas.shape[1] == 4
                 and self.smooth_l1_beta < 1e-5)
 
-    def _fused_losses(self, predictions, proposals):
+    def _fused_losses(self, predictions, proposals, dyn=None):
         scores, deltas = predictions
         gt_classes = torch.cat([p.gt_classes for p in proposals], dim=0)
+        if dyn is not None:
+            gt_classes = dyn.remap(gt_classes)
         prop = torch.cat([p.proposal_boxes.tensor for p in proposals], dim=0)
         gtb = torch.cat([(p.gt_boxes if p.has("gt_boxes") else p.proposal_boxes).tensor for p in proposals], dim=0)
         has_src = all(p.has("instance_source") for p in proposals)
@@ -369,10 +376,15 @@ class DeticFastRCNNOutputLayers(nn.Module):
         return losses
 
     def losses(self, predictions, proposals, classifier_info=(None, None, None)):
+        # DG :170-175: under the dynamic classifier classifier_info[1] = (inds, cls_id_map) and the labels are cls_id_map[gt_classes],
+        # the background = the last of the sampled columns (rows labelled -1, "ignore", stay -1: layers/dyn_vocab_ops.remap_labels)
+        dyn = classifier_info[1]
         if len(proposals) and self.fused_ok(predictions[0], predictions[1]):
-            return self._fused_losses(predictions, proposals)
+            return self._fused_losses(predictions, proposals, dyn)
         scores, deltas = predictions[0].float(), predictions[1].float()
         gt_classes = torch.cat([p.gt_classes for p in proposals], dim=0) if len(proposals) else torch.empty(0)
+        if dyn is not None and len(proposals):
+            gt_classes = dyn.remap(gt_classes)
         _log_classification_stats(scores, gt_classes)
         if len(proposals):
             prop = torch.cat([p.proposal_boxes.tensor for p in proposals], dim=0)
@@ -385,7 +397,8 @@ class DeticFastRCNNOutputLayers(nn.Module):
         has_src = len(proposals) > 0 and all(p.has("instance_source") for p in proposals)
         paste_src = torch.cat([p.instance_source for p in proposals if len(p)], dim=0) if has_src else None
         src = None if self.divergen_box_loss else paste_src
-        losses = {"loss_cls": loss_cls, "loss_box_reg": self.box_reg_loss(prop, gtb, deltas, gt_classes, src)}
+        losses = {"loss_cls": loss_cls, "loss_box_reg": self.box_reg_loss(prop, gtb, deltas, gt_classes, src,
+                                                                          num_classes=scores.shape[1] - 1 if dyn is not None else None)}
         if self.only_paste_sup and paste_src is not None and self.use_sigmoid_ce and scores.numel():
             losses["loss_paste_ins"], losses["loss_nopaste_ins"] = self.paste_split(scores, gt_classes, w, paste_src)
         return losses
@@ -458,8 +471,8 @@ class DeticFastRCNNOutputLayers(nn.Module):
         ce = F.binary_cross_entropy_with_logits(logits[:, :-1], target, reduction="none")
         return torch.sum(ce * w) / B
 
-    def box_reg_loss(self, prop, gtb, deltas, gt_classes, instance_source=None):
-        fg = ((gt_classes >= 0) & (gt_classes < self.num_classes)).nonzero().squeeze(1)
+    def box_reg_loss(self, prop, gtb, deltas, gt_classes, instance_source=None, num_classes=None):
+        fg = ((gt_classes >= 0) & (gt_classes < (self.num_classes if num_classes is None else num_classes))).nonzero().squeeze(1)
         fgd = deltas[fg] if deltas.shape[1] == 4 else deltas.view(-1, self.num_classes, 4)[fg, gt_classes[fg]]
         tgt = self.box2box_transform.get_deltas(prop[fg], gtb[fg])
         l = torch.abs(fgd - tgt) if self.smooth_l1_beta < 1e-5 else \

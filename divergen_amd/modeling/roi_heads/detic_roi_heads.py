@@ -291,21 +291,27 @@ class DeticCascadeROIHeads(nn.Module):
                                   float(self.cascade_ious[0]), self.num_classes, 1, Nmax, L.ptr(midx), L.ptr(labels), L.ptr(pos_idx),
                                   L.ptr(neg_idx), L.ptr(counts), L.stream()), "dgx_roi_label")
         before = self.__dict__.pop("_before_host_read", None)
+        dyn = self.__dict__.get("_dyn_vocab")
+        dyn_n = dyn.n_dev if dyn is not None and dyn.n is None else None      # the dynamic classifier's column count rides in this read
         if before is not None:
             # (meta_arch/custom_rcnn.py early_proposal_backward) the counts start their way to the host NOW; the work queued by
             # `before` runs behind them, so the device is busy while the host reads and issues the rest of the heads
             host = self.__dict__.get("_counts_host")
-            if host is None or host.numel() < 2 * B:
-                host = self.__dict__["_counts_host"] = torch.empty(max(2 * B, 32), dtype=torch.int32).pin_memory()
+            if host is None or host.numel() < 2 * B + 1:
+                host = self.__dict__["_counts_host"] = torch.empty(max(2 * B, 32) + 1, dtype=torch.int32).pin_memory()
                 self.__dict__["_counts_event"] = torch.cuda.Event()
             host[:2 * B].copy_(counts, non_blocking=True)
+            if dyn_n is not None:
+                host[2 * B:2 * B + 1].copy_(dyn_n, non_blocking=True)
             ev = self.__dict__["_counts_event"]
             ev.record()
             before()
             ev.synchronize()
-            c = host[:2 * B].tolist()
+            c = host[:2 * B + (dyn_n is not None)].tolist()
         else:
-            c = counts.tolist()                                       # THE device->host read of the step
+            c = (counts if dyn_n is None else torch.cat([counts, dyn_n])).tolist()      # THE device->host read of the step
+        if dyn_n is not None:
+            dyn.resolve(c[2 * B])
         perms, npos, nneg = [], [], []
         for i in range(B):
             k_pos = min(c[2 * i], int(self.batch_size_per_image * self.positive_fraction))
@@ -398,7 +404,7 @@ class DeticCascadeROIHeads(nn.Module):
         scores, deltas = self.box_predictor[stage](self.box_head[stage](x))
         return scores[:R], deltas[:R]
 
-    def _forward_box_train(self, features, proposals, targets):
+    def _forward_box_train(self, features, proposals, targets, dyn=None):
         """Training cascade with the stage hand-over (decode, clip, re-match, gather: `_create_proposals_from_boxes` +
         `_match_and_label_boxes` + `predict_boxes`) as ONE kernel per stage over the whole batch (dgx_cascade_refine) and
         the losses of each stage as one kernel pair (dgx_detic_losses).  An empty refined box -- a row the reference
@@ -431,6 +437,9 @@ class DeticCascadeROIHeads(nn.Module):
         st = get_event_storage()
         losses, valid, deltas = {}, None, None
         wts = self.box_predictor[0].box2box_transform
+        # dynamic classifier (DG custom_rcnn.py:159-165): one operand pair of the sampled vocabulary for the three predictors (the
+        # reference cuts it out of box_predictor[0]'s zs_weight), labels remapped per stage -- every hand-over relabels
+        ci = (dyn.classifier(self.box_predictor[0].cls_score), dyn, None) if dyn is not None else None
         for k in range(self.num_cascade_stages):
             if k > 0:
                 tr = self.box_predictor[k - 1].box2box_transform
@@ -449,11 +458,14 @@ class DeticCascadeROIHeads(nn.Module):
                 prop, valid = nb, nvalid
                 st.put_scalar("stage{}/roi_head/num_fg_samples".format(k), DeferredScalar(lambda f, B=B: f[0] / B, nfg))
                 st.put_scalar("stage{}/roi_head/num_bg_samples".format(k), DeferredScalar(lambda f, B=B, R=R: (R - f[0]) / B, nfg))
+            gtc_full = gtc
+            if dyn is not None:
+                gtc = dyn.remap(gtc)
             obs = self.__dict__.get("stage_observer")
-            if obs is not None:      # tests: the labels this stage trains on (hand-over to the CPU oracle)
-                obs(k, dict(boxes=prop, valid=valid, gt_classes=gtc, gt_boxes=gtb, counts=counts))
+            if obs is not None:      # tests: the labels this stage trains on (hand-over to the CPU oracle); gt_classes_full = before the remap
+                obs(k, dict(boxes=prop, valid=valid, gt_classes=gtc, gt_boxes=gtb, counts=counts, gt_classes_full=gtc_full))
             pred = self.box_predictor[k]
-            fused = box_stage_supported(self.box_head[k], pred)
+            fused = dyn is None and box_stage_supported(self.box_head[k], pred)
             # _ScaleGradient (cascade_rcnn.py:20-28, :150) sits on the pooled features: the fused stage leaves the factor to the pooler's
             # backward, which folds it into its interpolation table (no pass over the 25 MB pooled gradient)
             x = self.box_pooler.forward_rows(feats, prop, counts, pad_to=256, grad_scale=1.0 / self.num_cascade_stages if fused else 1.0)
@@ -470,14 +482,21 @@ class DeticCascadeROIHeads(nn.Module):
                 losses["loss_cls_stage{}".format(k)], losses["loss_box_reg_stage{}".format(k)] = loss_cls, loss_box
                 continue
             x = _ScaleGradient.apply(x, 1.0 / self.num_cascade_stages)
-            scores, deltas = pred(self.box_head[k](x))
+            scores, deltas = pred(self.box_head[k](x), ci) if ci is not None else pred(self.box_head[k](x))
             scores, deltas = scores[:R], deltas[:R]
             with st.name_scope("stage{}".format(k)):
                 sl = pred.losses_from_tensors(scores, deltas, gtc, prop, gtb, src)
             losses.update({n + "_stage{}".format(k): v for n, v in sl.items()})
         return losses
 
-    def _forward_box(self, features, proposals, targets=None, only_gt_proposals=False):
+    def _forward_box(self, features, proposals, targets=None, only_gt_proposals=False, dyn=None):
+        if dyn is not None:
+            if not (self.training and not only_gt_proposals and targets is not None and len(proposals)
+                    and sum(len(p) for p in proposals) > 0 and proposals[0].proposal_boxes.tensor.is_cuda
+                    and all(bp.fused_supported for bp in self.box_predictor)):
+                raise NotImplementedError("MODEL.DYNAMIC_CLASSIFIER: the sampled vocabulary trains through the GPU cascade (sigmoid CE, "
+                                          "class-agnostic L1 box regression) only")
+            return self._forward_box_train(features, proposals, targets, dyn)
         if (self.training and not only_gt_proposals and targets is not None and len(proposals) and sum(len(p) for p in proposals) > 0
                 and proposals[0].proposal_boxes.tensor.is_cuda and all(bp.fused_supported for bp in self.box_predictor)):
             return self._forward_box_train(features, proposals, targets)
@@ -551,6 +570,14 @@ class DeticCascadeROIHeads(nn.Module):
         prop, logits, pvalid, Ko = ws_proposals(boxes, scores, valid, sizes, self.ws_num_props, self.add_image_box, self.image_box_size)
         counts, R, dev = [Ko] * B, B * Ko, prop.device
         csr = label_csr([t._pos_category_ids for t in targets], dev)
+        from ...layers.dyn_vocab_ops import DynamicVocab
+        dyn = classifier_info[1] if isinstance(classifier_info[1], DynamicVocab) else None
+        if dyn is not None:
+            # DG detic_fast_rcnn.py:381-385: the labels of the list become columns of the sampled vocabulary (one remap for the three
+            # stages), the three predictors score against one prepared operand pair
+            if csr[1] is not None:
+                csr = (csr[0], dyn.remap(csr[1].long()).to(torch.int32), csr[2])
+            classifier_info = (dyn.classifier(self.box_predictor[0].cls_score), dyn, None)
         row0 = (ctypes.c_int * (B + 1))(*[i * Ko for i in range(B + 1)])
         gt0 = (ctypes.c_int * (B + 1))(*([0] * (B + 1)))
         img_h = (ctypes.c_float * B)(*[float(s[0]) for s in sizes])
@@ -582,6 +609,9 @@ class DeticCascadeROIHeads(nn.Module):
             if obs is not None:      # tests: what this stage's image-label loss sees
                 obs(k, dict(boxes=prop, valid=pvalid, scores=sc, prop_scores=ps, counts=counts, image_sizes=sizes))
             with st.name_scope("stage{}".format(k)):
+                if dyn is not None and len(targets[0]._pos_category_ids):
+                    # DG :382-383, inside each predictor's image_label_losses: the first image's first label, before the remap
+                    st.put_scalar("stats_label", float(targets[0]._pos_category_ids[0]))
                 sl = pred.image_label_losses(sc, pvalid, prop, counts, sizes, None, csr=csr, prop_scores=ps)
             losses.update({n + "_stage{}".format(k): v for n, v in sl.items()})
         out = ProposalBatch()
@@ -602,17 +632,28 @@ class DeticCascadeROIHeads(nn.Module):
                 if self.mask_on:        # DG detic_roi_heads.py:329-332: the mask head is not run
                     losses["loss_mask"] = torch.zeros((1,), device=proposals[0].objectness_logits.device)[0]
                 return proposals, losses
-            if any(c is not None for c in classifier_info):
+            from ...layers.dyn_vocab_ops import DynamicVocab
+            dyn = classifier_info[1] if isinstance(classifier_info[1], DynamicVocab) else None
+            if dyn is not None and (classifier_info[0] is not None or classifier_info[2] is not None or only_gt_proposals):
+                raise NotImplementedError("MODEL.DYNAMIC_CLASSIFIER on a box step: classifier_info = (None, DynamicVocab, None), no "
+                                          "only_gt_proposals pass")
+            if dyn is None and any(c is not None for c in classifier_info):
                 raise NotImplementedError("classifier_info on a box-annotated training step: the fused cascade trains on the built-in "
                                           "vocabulary (a per-call vocabulary, classifier_info[0], is built for image-labelled steps "
                                           "and for the predictor called on its own)")
-            proposals = self.label_and_sample_proposals(proposals, targets, only_gt_proposals)
+            self.__dict__["_dyn_vocab"] = dyn
+            try:
+                proposals = self.label_and_sample_proposals(proposals, targets, only_gt_proposals)
+            finally:
+                self.__dict__.pop("_dyn_vocab", None)
+            if dyn is not None:
+                dyn.resolve()       # (a sampler path without the fused read: a read of its own)
             if only_gt_proposals:
                 losses = self._forward_box(features, proposals, targets, only_gt_proposals=True)
                 if targets[0].has("gt_masks"):
                     losses.update({k: v * self.mask_weight for k, v in self._forward_mask(features, proposals).items()})
                 return proposals, losses
-            losses = self._forward_box(features, proposals, targets)
+            losses = self._forward_box(features, proposals, targets, dyn=dyn)
             stop_at = self.__dict__.pop("_early_box_backward", None)
             if stop_at is not None and losses and all(v.requires_grad for v in losses.values()):
                 # (meta_arch/custom_rcnn.py early_proposal_backward) the cascade's losses are back-propagated HERE, up to the feature maps in

@@ -72,6 +72,27 @@ class _ZeroShotLogits(torch.autograd.Function):
         return dx, None, None, gb, None
 
 
+class _ZeroShotLogitsF32(torch.autograd.Function):
+    """_ZeroShotLogits for the prepared operand pair of a sampled vocabulary (layers/dyn_vocab_ops.PreparedVocab): the forward keeps the
+    fp32 accumulators (dgx_zs_logits_f32) instead of the GEMM's bf16 result -- n is a few dozen columns, and an image step's loss reads
+    five selected rows, where the last bf16 bit of a logit shows; the backward is _ZeroShotLogits' (the bf16 GEMM on the transposed image)."""
+
+    @staticmethod
+    def forward(ctx, x, wimg, wimg_t, cls_bias, n):
+        from ... import _lib as L
+        x = x.contiguous()
+        R, D = x.shape
+        out = torch.empty(R, n, dtype=torch.float32, device=x.device)
+        L.check(L.lib().dgx_zs_logits_f32(L.ptr(x), L.ptr(wimg), R, D, n, wimg.shape[0], L.ptr(out), n, L.stream()), "dgx_zs_logits_f32")
+        if cls_bias is not None:
+            out = out + cls_bias.detach().float()
+        ctx.save_for_backward(wimg_t)
+        ctx.n, ctx.has_bias = n, cls_bias is not None
+        return out
+
+    backward = staticmethod(_ZeroShotLogits.backward)
+
+
 class ZeroShotClassifier(nn.Module):
     @configurable
     def __init__(self, input_shape, *, num_classes, zs_weight_path, zs_weight_dim=512, use_bias=0.0, norm_weight=True,
@@ -118,8 +139,13 @@ class ZeroShotClassifier(nn.Module):
 
     def forward(self, x, classifier=None):
         """x (R, in) -> logits (R, C + 1); with `classifier` (C', D), the per-call vocabulary of detic_fast_rcnn.py:445-446, its
-        rows are normalised per call and the result is (R, C')."""
-        if not x.is_cuda:       # host logic tests: the reference's arithmetic in torch
+        rows are normalised per call and the result is (R, C').  `classifier` may also be the prepared operand pair of such a
+        vocabulary (layers/dyn_vocab_ops.PreparedVocab, built by dgx_zs_gather: already normalised, cast, padded and transposed)."""
+        from ...layers.dyn_vocab_ops import PreparedVocab
+        prepared = classifier if isinstance(classifier, PreparedVocab) else None
+        if not x.is_cuda:
+            if prepared is not None:
+                raise RuntimeError("a prepared vocabulary (PreparedVocab) holds GPU operand images; CPU tensors take the raw `classifier` rows")       # host logic tests: the reference's arithmetic in torch
             h = F.linear(x, self.linear.weight, self.linear.bias)
             if classifier is not None:
                 zs = classifier.permute(1, 0).contiguous()
@@ -135,7 +161,11 @@ class ZeroShotClassifier(nn.Module):
             h = l2_normalize_rows(h, self.norm_temperature)
         elif h.dtype != BF16:
             h = h.to(BF16)
-        if classifier is not None:
+        if prepared is not None:
+            n, wimg, wimg_t = prepared.n1, prepared.W, prepared.Wt
+            if wimg.shape[1] != h.shape[1]:
+                raise ValueError("prepared vocabulary of width %d for embeddings of width %d" % (wimg.shape[1], h.shape[1]))
+        elif classifier is not None:
             c = classifier.detach().float().contiguous()
             n = c.shape[0]
             wimg, wimg_t = _pad_rows(l2_normalize_rows(c, 1.0) if self.norm_weight else c.to(BF16))
@@ -143,4 +173,5 @@ class ZeroShotClassifier(nn.Module):
             n = self.zs_weight.shape[1]
             wimg, wimg_t = self.zs_image()
         with torch.autocast("cuda", enabled=False):
-            return _ZeroShotLogits.apply(h, wimg, wimg_t, self.cls_bias if self.use_bias else None, n)
+            fn = _ZeroShotLogitsF32 if prepared is not None else _ZeroShotLogits
+            return fn.apply(h, wimg, wimg_t, self.cls_bias if self.use_bias else None, n)

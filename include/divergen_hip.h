@@ -727,6 +727,42 @@ int dgx_fed_class_mask(const int64_t* gt_classes, int R, const float* prob, cons
                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Dynamic classifier (MODEL.DYNAMIC_CLASSIFIER): the sampled per-batch vocabulary of
+ * DG/divergen/modeling/meta_arch/custom_rcnn.py:159-165, :226-247 (csrc/dyn_vocab.hip).
+ *
+ * dgx_dyn_class_sample = _sample_cls_inds (get_fed_loss_inds, utils.py:16-28, + the cls_id_map of :244-246), one workgroup.
+ *   labels  i64 (G), G >= 0 (NULL when 0): entries outside [0, C) are not classes and are skipped (the reference asserts on them)
+ *   prob0   f32 (C+1) >= 0, the sampling weights (the last entry, the background, is not read); expo f32 (C+1), Exponential(1)
+ *           draws of the caller's generator: multinomial without replacement IS the top-k of prob0 / expo
+ *   C <= num_classes; S = NUM_SAMPLE_CATS
+ *   inds    i64, capacity max(S, min(G, num_classes)): inds[0:a] = the distinct labels ascending; when a < S, then the
+ *           min(S - a, #{c < C not appearing, prob0[c] > 0}) classes with the largest prob0[c] / expo[c], key descending, equal
+ *           keys lower index first (fp32 IEEE division, the keys compared as fp32)
+ *   n       i32 (1) = the number of entries written
+ *   cls_id_map i64 (num_classes + 1): cls_id_map[inds[j]] = j, every other entry (the background's included) = n
+ * Upper limit: C + 1 <= 32768 and 4 C + 4 ceil(C / 32) + 8 pow2ceil(min(S, C)) <= 153600 bytes of LDS (C = 32767 with S <= 2048;
+ * C = S up to 8192); DGX_ERR_UNSUPPORTED above.  O(C + k log^2 k) for k drawn classes; integer LDS atomics only: two runs give the
+ * same bits.
+ *
+ * dgx_zs_gather = both GEMM operand images of the sub-vocabulary: W bf16 (pad8(n+1), D) and Wt bf16 (D, pad8(n+1)), Wt = W^T.
+ *   zs      zs_weight f32 (D, C+1), the classifier's buffer (its cached bf16 image is not a source: a second rounding in front of the
+ *           re-normalisation would show in the losses)
+ *   rows 0..n-1 = columns inds[j] of zs_weight, divided by max(||column||_2, 1e-12) in fp32 when `normalize`
+ *   (zero_shot_classifier.py:77-79), rounded to bf16 (nearest even); row n (the background) and the pad rows are zeros.
+ *   inds i64 (n) on the device, n on the host.
+ *
+ * dgx_zs_logits_f32: y f32 (R, n1), row stride ldy = x bf16 (R, D) times the first n1 rows of W bf16 (npad, D) transposed (the pair
+ *   dgx_zs_gather wrote), fp32 accumulation in ascending k, NOT rounded to bf16: the logits of a sampled vocabulary (zero_shot_classifier.py:84).
+ *
+ * dgx_remap_labels: out[r] = cls_id_map[in[r]] for 0 <= in[r] <= num_classes, out[r] = in[r] otherwise (the ignore rows, -1, that
+ * dgx_cascade_refine writes stay -1; torch's cls_id_map[-1] would make them background). */
+int dgx_dyn_class_sample(const int64_t* labels, int G, const float* prob0, const float* expo, int C, int num_classes, int S,
+                         int64_t* inds, int64_t* cls_id_map, int32_t* n, void* stream);
+int dgx_zs_gather(const float* zs, int D, int C, const int64_t* inds, int n, int normalize, void* W, void* Wt, void* stream);
+int dgx_zs_logits_f32(const void* x, const void* W, int R, int D, int n1, int npad, float* y, int64_t ldy, void* stream);
+int dgx_remap_labels(const int64_t* in, int64_t R, const int64_t* cls_id_map, int num_classes, int64_t* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Hand-over between two cascade stages for all images of the batch in one launch
  * (detic_roi_heads.py:192-244 `_forward_box`, `_create_proposals_from_boxes`, :136-190 `_match_and_label_boxes`):
  * boxes = clip(apply_deltas(deltas, prop)) (box_regression.py:76-118, class-agnostic), valid_out = valid_in & nonempty,

@@ -6,12 +6,22 @@ Swin size / resolution / batch on the command line:
 --loss wsddn (alias wsod) turns on MODEL.ROI_BOX_HEAD.WS_PROP_SCORE and WITH_SOFTMAX_PROP and also reports, from one profiled image step,
 the device time of the three dgx_wsddn_loss launches per cascade stage next to the bytes they must move (two reads and two writes of
 R x (C+1) bf16 elements per stage).
+
+--vocab N builds a synthetic open-vocabulary classifier of N classes (USE_ZEROSHOT_CLS on random embeddings, random image counts) and times
+the same two steps on the whole vocabulary; with --dynamic also MODEL.DYNAMIC_VOCAB + MODEL.DYNAMIC_CLASSIFIER (NUM_SAMPLE_CATS from
+--sample-cats), and the device time of the four kernels of csrc/dyn_vocab.hip from one profiled box step and one profiled image step
+next to the bytes they must move:
+
+    python tools/image_label_bench.py --vocab 22047              # static: R x (N + 1) logits per cascade stage
+    python tools/image_label_bench.py --vocab 22047 --dynamic    # dynamic: R x (NUM_SAMPLE_CATS + 1)
 """
 import argparse
 import json
 import os
 import sys
+import tempfile
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,7 +35,12 @@ def main():
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--loss", default="max_size")
+    ap.add_argument("--vocab", type=int, default=0)
+    ap.add_argument("--dynamic", action="store_true")
+    ap.add_argument("--sample-cats", type=int, default=50)
     a = ap.parse_args()
+    if a.dynamic and not a.vocab:
+        ap.error("--dynamic needs --vocab N")
     from divergen_amd.config import get_cfg
     from divergen_amd.data import synthetic_batch
     from divergen_amd.engine import total_loss
@@ -38,6 +53,17 @@ def main():
     cfg.merge_from_list(["MODEL.SWIN.SIZE", a.size, "WITH_IMAGE_LABELS", True, "MODEL.ROI_BOX_HEAD.IMAGE_LABEL_LOSS", a.loss,
                          "MODEL.ROI_BOX_HEAD.ADD_IMAGE_BOX", True,
                          "MODEL.ROI_BOX_HEAD.CAT_FREQ_PATH", os.path.join(ROOT, "configs", "metadata", "lvis_v1_train_cat_info.json")])
+    if a.vocab:
+        tmp = tempfile.mkdtemp()
+        rs = np.random.RandomState(0)
+        npy, freq = os.path.join(tmp, "emb.npy"), os.path.join(tmp, "freq.json")
+        np.save(npy, rs.standard_normal((a.vocab, 512)).astype(np.float32))
+        json.dump([{"id": i + 1, "image_count": int(c)} for i, c in enumerate(rs.randint(0, 2000, a.vocab))], open(freq, "w"))
+        cfg.merge_from_list(["MODEL.ROI_BOX_HEAD.USE_ZEROSHOT_CLS", True, "MODEL.ROI_BOX_HEAD.ZEROSHOT_WEIGHT_PATH", npy,
+                             "MODEL.ROI_HEADS.NUM_CLASSES", a.vocab, "MODEL.ROI_BOX_HEAD.USE_BIAS", -4.6, "MODEL.ROI_BOX_HEAD.USE_FED_LOSS", False,
+                             "MODEL.ROI_BOX_HEAD.CAT_FREQ_PATH", freq])
+        if a.dynamic:
+            cfg.merge_from_list(["MODEL.DYNAMIC_VOCAB", True, "MODEL.DYNAMIC_CLASSIFIER", True, "MODEL.NUM_SAMPLE_CATS", a.sample_cats])
     wsddn = a.loss in ("wsddn", "wsod")
     if wsddn:
         cfg.merge_from_list(["MODEL.ROI_BOX_HEAD.WS_PROP_SCORE", True, "MODEL.ROI_BOX_HEAD.WITH_SOFTMAX_PROP", True])
@@ -61,6 +87,8 @@ def main():
         opt.step()
 
     out = {"size": a.size, "res": a.res, "batch": a.batch, "steps": a.steps, "image_label_loss": a.loss}
+    if a.vocab:
+        out.update(vocab=a.vocab, dynamic=a.dynamic, sample_cats=a.sample_cats if a.dynamic else None)
     with EventStorage(0):
         for name, batch in (("box", box), ("image", img)):
             for _ in range(3):
@@ -73,6 +101,29 @@ def main():
             e1.record()
             torch.cuda.synchronize()
             out["ms_per_%s_step" % name] = round(e0.elapsed_time(e1) / a.steps, 3)
+        if a.dynamic:
+            from torch.profiler import ProfilerActivity, profile
+            kernels = ("dyn_class_sample_kernel", "zs_gather_kernel", "remap_labels_kernel", "zs_logits_f32_kernel")
+            for name, batch in (("box", box), ("image", img)):
+                with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                    step(batch)
+                    torch.cuda.synchronize()
+                us, calls = {}, {}
+                for ev in prof.events():
+                    for k in kernels:
+                        if k in ev.name:
+                            us[k] = us.get(k, 0.0) + ev.device_time_total
+                            calls[k] = calls.get(k, 0) + 1
+                out["dyn_us_per_%s_step" % name] = {k: round(v, 2) for k, v in us.items()}
+                out["dyn_launches_per_%s_step" % name] = calls
+            S, D = a.sample_cats, 512
+            Cw = len(model.freq_weight)
+            n1p = (S + 1 + 7) // 8 * 8
+            out["dyn_bytes"] = {"dyn_class_sample_kernel(box)": 8 * (Cw + 1) + 8 * (C + 1) + 8 * S,          # prob0 + expo read, cls_id_map + inds written
+                                "dyn_class_sample_kernel(image)": 8 * (C + 1) + 8 * (C + 1) + 8 * S,
+                                "zs_gather_kernel": 2 * 4 * S * D + 2 * 2 * n1p * D,                       # S columns read twice (norm, value), W and Wt written
+                                "remap_labels_kernel(per row)": 24,                                        # label read, map entry read, label written
+                                "zs_logits_f32_kernel(per row)": 2 * D + 4 * (S + 1)}                      # a bf16 row read, S + 1 fp32 logits written (+ W once)
         if wsddn:
             from torch.profiler import ProfilerActivity, profile
             with profile(activities=[ProfilerActivity.CUDA]) as prof:
