@@ -210,6 +210,7 @@ SIGNATURES = {
     "dgx_zero_ranges_f32": (c_i, [c_p, c_p, c_i64, c_p]),
     "dgx_sgd_ema_step": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i64, c_f, c_f, c_i, c_f, c_f, c_f, c_p, c_i, c_f, c_p, c_p, c_i, c_p, c_p]),
     "dgx_clip_coef_workspace_floats": (c_i64, []),
+    "dgx_optim_grid_quads": (c_i64, []),
     "dgx_clip_coef_f32": (c_i, [c_p, c_i64, c_f, c_f, c_p, c_p, c_p]),
     "dgx_adamw_ema_step": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_f,
                                  c_p, c_p, c_i, c_p, c_p]),

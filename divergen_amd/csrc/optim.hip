@@ -5,6 +5,8 @@
 // before optimizer.step() (train_net.py:262-284).
 #include "dgx_common.h"
 
+constexpr int STEP_BLOCKS = 16384;      // grid cap of the two step kernels (256 lanes each): dgx_optim_grid_quads()
+
 __global__ __launch_bounds__(256) void adamw_ema_kernel(float4* __restrict__ p, const float4* __restrict__ g,
                                                         float4* __restrict__ m, float4* __restrict__ v,
                                                         float4* __restrict__ ema, uint2* __restrict__ pbf, int64_t n4,
@@ -50,7 +52,7 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(float4* __restrict__ p, 
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             float gr = ge[k] * gscale;
-            gr = fminf(fmaxf(gr, -clip), clip);
+            gr = gr != gr ? gr : fminf(fmaxf(gr, -clip), clip);      // a NaN gradient stays NaN (clamp_ propagates it); fmaxf alone would absorb it into -clip
             pe[k] *= 1.0f - lre * wd;
             me[k] = me[k] + (gr - me[k]) * (1.0f - b1);
             ve[k] = ve[k] * b2 + (1.0f - b2) * gr * gr;
@@ -75,7 +77,7 @@ extern "C" int dgx_adamw_ema_step_scaled(float* p, const float* g, float* m, flo
     const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
     const float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
     const int64_t n4 = n / 4;
-    const int grid = (int)((n4 + 255) / 256 < 16384 ? (n4 + 255) / 256 : 16384);
+    const int grid = (int)((n4 + 255) / 256 < STEP_BLOCKS ? (n4 + 255) / 256 : STEP_BLOCKS);
     hipLaunchKernelGGL(adamw_ema_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (float4*)p, (const float4*)g,
                        (float4*)m, (float4*)v, (float4*)ema, (uint2*)p_bf16, n4, lr, beta1, beta2, eps, weight_decay,
                        clip_value > 0 ? clip_value : INFINITY, grad_scale, grad_scale_dev, bc1, bc2s, ema_decay, lr_scale, seg_end,
@@ -128,7 +130,7 @@ __global__ __launch_bounds__(256) void sgd_ema_kernel(float4* __restrict__ p, co
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             float d = ge[k] * gscale;
-            d = fminf(fmaxf(d, -clip), clip);
+            d = d != d ? d : fminf(fmaxf(d, -clip), clip);           // NaN stays NaN, as in the AdamW kernel
             d = d + wd * pe[k];
             if (mom != 0.f) {
                 be[k] = first ? d : mom * be[k] + d;
@@ -151,7 +153,7 @@ extern "C" int dgx_sgd_ema_step(float* p, const float* g, float* buf, float* ema
         (nesterov && momentum <= 0.f))
         return DGX_ERR_BAD_ARG;
     const int64_t n4 = n / 4;
-    const int grid = (int)((n4 + 255) / 256 < 16384 ? (n4 + 255) / 256 : 16384);
+    const int grid = (int)((n4 + 255) / 256 < STEP_BLOCKS ? (n4 + 255) / 256 : STEP_BLOCKS);
     hipLaunchKernelGGL(sgd_ema_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (float4*)p, (const float4*)g, (float4*)buf,
                        (float4*)ema, (uint2*)p_bf16, n4, lr, momentum, nesterov, weight_decay, clip_value > 0 ? clip_value : INFINITY,
                        grad_scale, grad_scale_dev, step == 1 ? 1 : 0, ema_decay, lr_scale, seg_end, n_seg, found_inf);
@@ -184,12 +186,13 @@ __global__ __launch_bounds__(64) void clip_coef_kernel(const float* __restrict__
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     if (threadIdx.x == 0) {
         const float norm = (float)sqrt(s) * fabsf(gscale);
-        out[0] = fminf(1.0f, max_norm / (norm + 1e-6f));
+        out[0] = norm != norm ? norm : fminf(1.0f, max_norm / (norm + 1e-6f));      // a NaN norm gives a NaN coefficient, as clip_grad_norm_ does
         out[1] = norm;
     }
 }
 
 extern "C" int64_t dgx_clip_coef_workspace_floats(void) { return CLIP_BLOCKS; }
+extern "C" int64_t dgx_optim_grid_quads(void) { return (int64_t)STEP_BLOCKS * 256; }
 extern "C" int dgx_clip_coef_f32(const float* g, int64_t n, float grad_scale, float max_norm, float* workspace, float* out2,
                                  void* stream) {
     if (!g || !workspace || !out2 || n <= 0 || (n & 3) || !(max_norm > 0.f)) return DGX_ERR_BAD_ARG;

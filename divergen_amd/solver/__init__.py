@@ -338,6 +338,25 @@ class FlatArena:
 ARENA_LAYOUT_VERSION = 3
 
 
+def check_quad_multipliers(arena, lr_multipliers):
+    """The step kernels (csrc/optim.hip) move 4 elements per lane and look the lr multiplier of a whole quad up by its FIRST element.
+    The members of a parameter group lie back to back without alignment, so a quad may hold the tail of one parameter and the head of
+    the next: both must then carry the same multiplier, or up to 3 elements would be stepped with the neighbour's learning rate.
+    Raises ValueError naming the two parameters."""
+    offs, names = arena.offsets, arena.names
+    for i in range(1, len(offs)):
+        if offs[i] % 4 == 0:
+            continue
+        q0, j = offs[i] // 4 * 4, i - 1
+        while j > 0 and offs[j] > q0:
+            j -= 1
+        if lr_multipliers[i] != lr_multipliers[j]:
+            raise ValueError("parameters '%s' (lr multiplier %g) and '%s' (lr multiplier %g) share the 4-element group at arena offset "
+                             "%d, which the optimizer kernel steps with ONE learning rate: give both the same multiplier "
+                             "(SOLVER.BACKBONE_MULTIPLIER / CUSTOM_MULTIPLIER_NAME must match all members of a parameter group or none)"
+                             % (names[j], lr_multipliers[j], names[i], lr_multipliers[i], q0))
+
+
 class FusedAdamWEMA:
     """Optimizer + EMA over a FlatArena.  API mirrors torch.optim (step/zero_grad/state_dict) as far
     as the training loop and the checkpointer need."""
@@ -353,6 +372,7 @@ class FusedAdamWEMA:
         self.step_count = 0
         self.lr_scale = self.seg_end = None
         if lr_multipliers is not None and any(abs(x - 1.0) > 0 for x in lr_multipliers):
+            check_quad_multipliers(arena, lr_multipliers)
             self.lr_scale = torch.tensor(lr_multipliers, dtype=torch.float32, device=arena.p.device)
             self.seg_end = torch.tensor(arena.segment_ends(), dtype=torch.int64, device=arena.p.device)
         self.param_groups = [{"lr": lr}]
@@ -450,6 +470,7 @@ class FusedSGDEMA(FusedAdamWEMA):
         self.step_count = 0
         self.lr_scale = self.seg_end = None
         if lr_multipliers is not None and any(abs(x - 1.0) > 0 for x in lr_multipliers):
+            check_quad_multipliers(arena, lr_multipliers)
             self.lr_scale = torch.tensor(lr_multipliers, dtype=torch.float32, device=arena.p.device)
             self.seg_end = torch.tensor(arena.segment_ends(), dtype=torch.int64, device=arena.p.device)
         self.param_groups = [{"lr": lr}]

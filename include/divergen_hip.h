@@ -471,7 +471,10 @@ int dgx_remove_background(const uint8_t* image, const uint8_t* masks, int n, int
  *   p,g,m,v,ema f32 (n); lr_scale f32 (n_seg) per-segment lr multiplier, seg_end i64 (n_seg)
  *   exclusive end offsets (or both NULL);  grad_scale multiplies g first (1/loss_scale, 1/world);
  *   found_inf i32 (1) optional: if *found_inf != 0 the step is skipped (GradScaler semantics);
- *   p_bf16 optional. */
+ *   p_bf16 optional.  The value clip keeps a NaN gradient element NaN (as clamp_ does): it reaches m, v, p and
+ *   the shadow of that element instead of becoming a gradient of -clip; +-inf clamps to +-clip.  The lr
+ *   multiplier of a whole 4-element group is looked up by its first element: segments that share such a
+ *   group must carry the same multiplier (solver.check_quad_multipliers refuses anything else). */
 int dgx_adamw_ema_step(float* p, const float* g, float* m, float* v, float* ema, void* p_bf16,
                        int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
                        float clip_value, float grad_scale, int step, float ema_decay,
@@ -496,12 +499,17 @@ int dgx_sgd_ema_step(float* p, const float* g, float* buf, float* ema, void* p_b
                      const int32_t* found_inf, void* stream);
 /* FullModelGradientClippingOptimizer (custom_solver.py:46-60: torch.nn.utils.clip_grad_norm_ over all parameters) without a host
  * read: out2[0] = min(1, max_norm / (||g * grad_scale||_2 + 1e-6)), out2[1] = the norm; out2 is what dgx_sgd_ema_step takes as
- * grad_scale_dev.  workspace: dgx_clip_coef_workspace_floats() floats.  Deterministic (fixed partial order, double fold). */
+ * grad_scale_dev.  workspace: dgx_clip_coef_workspace_floats() floats.  Deterministic (fixed partial order, double fold).
+ * A NaN gradient element gives a NaN norm AND a NaN coefficient (clip_grad_norm_ does the same), so the step that takes it spreads the
+ * NaN over every weight, where it is seen. */
 /* g[first .. first + count) = 0 for n ranges, ranges i64 (n, 2) DEVICE, first / count multiples of 4, count <= 65536: the gradient
  * arena minus the segments their first writer overwrites (`optimizer.zero_grad()` of train_net.py:248-304 without touching what the
  * weight-gradient launches rewrite anyway). */
 int dgx_zero_ranges_f32(float* g, const int64_t* ranges, int64_t n, void* stream);
 int64_t dgx_clip_coef_workspace_floats(void);
+/* Quads (4 floats) that one sweep of the capped grid of dgx_adamw_ema_step / dgx_sgd_ema_step covers: grid cap x 256 lanes.  An arena
+ * of more quads makes the kernels' loops run again (the tests size their cases from this value). */
+int64_t dgx_optim_grid_quads(void);
 int dgx_clip_coef_f32(const float* g, int64_t n, float grad_scale, float max_norm, float* workspace, float* out2, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
