@@ -1,0 +1,518 @@
+"""float64 restatements of the convolution kernels -- the implicit 3x3 GEMM (csrc/gemm_common.h g_a_voff / g_a_soff, gemm_nt.hip
+dgx_conv3x3_gemm[_multi]), the tap-problem weight / bias gradient (wgrad256.hip dgx_conv3x3_wgrad_bias[_multi]), the zero-bordered copies
+and the column-matrix form (im2col.hip), ConvTranspose2d(2, 2) as GEMM + pixel shuffle -- written from the definitions as index arithmetic
+on the NHWC / OHWI layouts the kernels use (no torch.nn.functional convolution is called here), the per-element a-priori bounds the GPU
+test holds the kernels to (tests/test_gpu_conv_numerics.py), the case tables both test files use, and the mutants.  Plain torch on the
+CPU; no project kernel is called from here.  tests/test_host_conv_ref.py pins the restatements on torch's float64 convolutions and their
+autograd, shows that fp32 CPU evaluations of the contract (bf16 operands, fp32 accumulation in three orders, one rounding) stay inside
+every bound on every case, that every mutant leaves one, and that the plans in the tables are what gemm_plan.h / plan256 decide.
+
+Every restatement returns (ref, A, n): the float64 value, the SAME contraction over absolute values, and the number of addends of an
+element in the kernel's contraction (all nine taps counted, + 1 for the bias or the beta * g0 term; for dW / db the padded row count
+N (H + 2) (W + 2), which is what the nine tap problems run over).
+
+Bounds, u = 2^-24, per element, no absolute floor (the host test asserts that every compared reference value is 0 or a normal bf16
+magnitude):
+  bf16 results (y, dx, deconvolution outputs, bf16 col2im)   |got - ref| <= 2^-8 |ref| + ACC_FACTOR n u A (1 + 2^-8)
+  fp32 results (dW, db, f32 col2im)                          |got - ref| <= u |ref| + ACC_FACTOR n u A        (|beta g0| inside A)
+  im2col, the zero-bordered copies, the deconvolution shuffles: exact.
+n u A is the textbook worst case of an fp32 summation of exact products in ANY order (bf16 x bf16 is exact in fp32), which covers the
+split-K slabs, the fold, the M-slabs and the reduce; a ReLU is 1-Lipschitz, so the bound of the pre-activation holds behind it.  It
+rests on one assumption: an MFMA accumulation errs no more than one fp32 addition per product.
+  two roundings: the stride-2 input gradient of the Python layer is gemm (dcol, rounded to bf16) + col2im (fp32 sum of <= 9 bf16 values,
+  rounded to bf16).  Its bound is the composition, term by term: `two_rounding_bound`.  The one-rounding bound does not describe this
+  path: an fp32 CPU evaluation of the path's own contract sits 33 - 71 x above it on the two stride-2 cases of the GPU test (where the
+  nine rounded taps cancel) and at 0.79 - 0.87 of the composed bound, the same figures the kernels give.
+
+ACC_FACTOR = 1: the MI355X run of tests/test_gpu_conv_numerics.py needed no factor on the accumulation term.  Worst measured
+|err| / bound per kernel and output of that run (every case of the tables below, all three input kinds, every plan):
+  kernel                        output  worst   where
+  dgx_conv3x3_gemm              y       0.973   (1, 1, 200, 64, 64) postrelu, bias + ReLU, gemm_nt without workspace
+  dgx_conv3x3_gemm              dx      0.979   (1, 1, 200, 64, 64) postrelu, ReLU', gemm_nt without workspace
+  dgx_conv3x3_gemm_multi        y       0.973   Cin 64 / Cout 136, levels 12 x 12 and 1 x 1, bias, gemm_nt
+  dgx_conv3x3_wgrad_bias        dW      0.081   (1, 2, 2, 64, 64) ordinary, S = 1, beta = 1
+  dgx_conv3x3_wgrad_bias        db      0.055   (1, 2, 2, 64, 64) postrelu, S = 1, beta = 1
+  dgx_conv3x3_wgrad_bias_multi  dW      0.001   Cin 256 / Cout 256, 27 slabs of 128 rows, beta = 1
+  dgx_conv3x3_wgrad_bias_multi  db      0.000
+  dgx_col2im3x3                 dx      0.996   (1, 8, 6, 8) stride 2, bf16, cancelling
+  conv_ops.conv3x3 (stride 1)   y / dx  0.961 / 0.980    dW / db  0.008 / 0.001
+  conv_ops.conv3x3 (stride 2)   y / dx  0.981 / 0.874    dW / db  0.102 / 0.000      (dx against two_rounding_bound)
+  conv_ops.deconv2x2            y / dx  0.994 / 0.984    dw / db  0.005 / 0.000
+  conv_ops.Conv2d in an arena   y       0.908            dW / db  0.003 / 0.000      (two accumulating steps)
+The bf16 figures are the one rounding itself (half an ulp at the bottom of a binade is 2^-8 |ref| to within 2^-8 of it: the host-side
+fp32 evaluation reaches 0.96 too); what the accumulation adds shows in the fp32 outputs, which stay below a fifth of n u A.  The pad
+copies, im2col and the one-hot launches were bit-exact, and every launch ran the plan of its row.
+
+Case tables.  GEMM_ROWS: geometry (N, H, W, Cin, Cout) -> (bm, bn, splits with the 64 MB workspace) of the forward launch and, where
+Cout % 64 == 0 (the C ABI wants whole K-tiles), of the input-gradient launch (Cin and Cout exchanged); the form is 1 (loader-wave) by
+default and 0 with dgx_dev("gemm_lw", 0), splits = 1 without a workspace.  WGRAD_ROWS: geometry -> (S, 32-row stages per slab, reduce
+form) as `plan256` decides, restated in `wgrad_plan`.
+
+Mutants: wrong restatements of the kind the kernels could produce (FWD_MUTANTS, WGRAD_MUTANTS, STRIDE2_MUTANTS; the text next to each).
+A mutant is DEFINED on a case when its float64 value differs from the restatement's at all; it must then leave the bound somewhere."""
+import torch
+
+U = 2.0 ** -24
+EB = 2.0 ** -8
+ACC_FACTOR = 1.0
+F32, BF16, F64 = torch.float32, torch.bfloat16, torch.float64
+WS_BYTES = 64 << 20            # layers/gemm_ops.WS_BYTES: the split-K scratch the Python layer hands to every implicit GEMM
+BF16_MIN_NORMAL, BF16_MAX = 2.0 ** -126, (2.0 - 2.0 ** -7) * 2.0 ** 127
+
+FWD_MUTANTS = {
+    "row_wrap": "pixel x = -1 reads the previous row's last pixel (a wrong wp)",
+    "image_wrap": "y = -1 reads the previous image's last row",
+    "taps_transposed": "w[co][kx][ky] used for tap (ky, kx)",
+    "taps_flipped": "w[co][2-ky][2-kx]: the input-gradient twin used in the forward pass",
+    "corner_tap": "one tap (the one pointing inward, the centre on one-pixel-wide maps) missing at the four corner pixels of each image only",
+    "chunk8": "the last 8 channels of the last tap dropped",
+    "split_tail": "the last K-tile of every split dropped",
+    "bias_per_split": "the bias added once per split",
+    "relu_first": "ReLU before the bias",
+    "row_tail": "rows behind the last full row tile zero",
+    "col_tail": "columns behind the last full 256 columns zero",
+}
+WGRAD_MUTANTS = {
+    "border_counted": "border positions of dy counted (they hold the nearest pixel instead of zero)",
+    "step_tail": "the last partial 32-row step of every slab dropped",
+    "last_slab": "the last slab dropped",
+    "beta_ignored": "beta ignored",
+    "beta_per_slab": "beta applied once per slab",
+    "taps_transposed": "dW[co][kx][ky] written for tap (ky, kx)",
+    "db_tap4_shift": "the bias gradient read behind tap 4's offset of x, (wp + 1) Cin elements, instead of dy's (wp + 1) Cout",
+}
+STRIDE2_MUTANTS = {
+    "half_out": "Ho = H / 2 instead of (H - 1) / 2 + 1",
+    "parity": "odd and even taps swapped in col2im (ty = y - ky)",
+}
+
+GEOMS = [(1, 1, 1, 64, 64), (2, 7, 9, 64, 8), (3, 5, 9, 64, 72), (1, 1, 200, 64, 64), (1, 200, 1, 64, 64), (2, 12, 12, 64, 192),
+         (2, 13, 18, 128, 264), (1, 6, 5, 192, 64), (1, 23, 17, 320, 24), (2, 16, 16, 256, 256)]
+# geometry -> {"fwd": (bm, bn, splits), "dgrad": (bm, bn, splits)}
+GEMM_ROWS = {
+    (1, 1, 1, 64, 64): {"fwd": (128, 128, 2), "dgrad": (128, 128, 2)},              # M = 1
+    (2, 7, 9, 64, 8): {"fwd": (128, 128, 2)},                                       # M = 126: one partial row tile, narrowest Cout
+    (3, 5, 9, 64, 72): {"fwd": (128, 128, 2)},                                      # M = 135: image boundaries inside a tile, 7-row second tile
+    (1, 1, 200, 64, 64): {"fwd": (128, 128, 2), "dgrad": (128, 128, 2)},            # one row
+    (1, 200, 1, 64, 64): {"fwd": (128, 128, 2), "dgrad": (128, 128, 2)},            # one column (wp = 3)
+    (2, 12, 12, 64, 192): {"fwd": (128, 192, 2), "dgrad": (128, 128, 6)},           # 192-column tile; dgrad: K = 27 tiles cut 5x5 + 2
+    (2, 13, 18, 128, 264): {"fwd": (128, 128, 4)},                                  # three column tiles, the last 8 wide; 18 cut 5+5+5+3
+    (1, 6, 5, 192, 64): {"fwd": (128, 128, 6), "dgrad": (128, 192, 2)},             # conv_kc = 3; 27 K-tiles cut 5x5 + 2
+    (1, 23, 17, 320, 24): {"fwd": (128, 128, 9)},                                   # conv_kc = 5; 9 splits of 5
+    (2, 16, 16, 256, 256): {"fwd": (128, 256, 9), "dgrad": (128, 256, 9)},          # the tower layer: 128 x 256 tile, 9 splits of 4
+}
+TILES = [(256, 192), (192, 192), (128, 192), (192, 256), (128, 256), (256, 128), (128, 128)]      # gemm_plan.h nt_stages
+FORCED_GEOM = (2, 13, 18, 128, 264)
+MULTI_LEVELS = [(2, 12, 12), (2, 6, 6), (2, 3, 3), (2, 2, 1), (1, 1, 1)]
+MULTI_WIDTHS = [(64, 136), (256, 256)]
+MULTI_PLAN = (128, 256, 1)          # 7 row tiles of 128 (no saving from 192), Cout > 128: one 256-column tile, never split
+
+WGRAD_ROWS = {
+    (1, 2, 2, 64, 64): (1, 1, "direct"),            # S = 1: written straight with beta, 16 live rows of one 32-row step
+    (1, 3, 4, 64, 64): (1, 1, "direct"),            # 30 live rows
+    (1, 4, 4, 64, 64): (2, 1, "lpq1"),              # last slab 4 rows
+    (2, 7, 9, 64, 8): (7, 1, "lpq1"),               # Cout = 8
+    (2, 13, 18, 128, 264): (10, 2, "lpq1"),         # two Cout tiles (256 + 8), two bias column blocks
+    (1, 23, 17, 320, 24): (8, 2, "lpq1"),           # two Cin tiles (256 + 64), last slab 27 rows
+    (2, 16, 16, 256, 256): (21, 1, "lpq1"),         # output too large for 16 lanes per quad
+    (2, 20, 20, 64, 64): (16, 2, "lpq16"),          # first LPQ = 16
+    (2, 32, 32, 64, 64): (25, 3, "lpq16"),          # pipeline tails: odd
+    (2, 36, 36, 64, 64): (23, 4, "lpq16"),          # 4k
+    (2, 42, 42, 64, 64): (25, 5, "lpq16"),          # 4k + 1
+    (2, 48, 48, 64, 64): (27, 6, "lpq16"),          # 4k + 2
+    (2, 52, 52, 64, 64): (27, 7, "lpq16"),          # 4k + 3
+    (2, 56, 56, 64, 64): (27, 8, "lpq16"),          # 2 x 4
+}
+WGRAD_MULTI_LEVELS = MULTI_LEVELS + [(2, 32, 32)]
+WGRAD_MULTI_WIDTHS = [(256, 256), (64, 8), (64, 264)]
+PAD_SHAPES = [(1, 1, 1, 8), (2, 5, 9, 64), (3, 7, 1, 264), (1, 1, 6, 72)]
+COL_SHAPES = [(1, 1, 1, 8), (2, 2, 9, 24), (2, 13, 18, 16), (1, 7, 5, 256), (1, 8, 6, 8)]
+INPUT_KINDS = ("ordinary", "cancelling", "postrelu")
+
+
+# ------------------------------------------------------------------ bounds
+def bf16_bound(ref, A, n):
+    return EB * ref.abs() + ACC_FACTOR * n * U * A * (1.0 + EB)
+
+
+def f32_bound(ref, A, n):
+    return U * ref.abs() + ACC_FACTOR * n * U * A
+
+
+def two_rounding_bound(ref, A1, n1, S1, n2):
+    """A bf16 result summed in fp32 from n2 bf16 intermediates, each the rounding of an n1-term fp32 accumulation: S1 = the sum of the
+    intermediates' magnitudes, A1 = the sum of their A.  Every intermediate errs by at most 2^-8 |v| + n1 u a (1 + 2^-8) (its own bf16
+    bound); the fp32 sum of the n2 rounded values adds n2 u (S1 + that); the last rounding 2^-8 of the computed sum."""
+    inner = EB * S1 + ACC_FACTOR * n1 * U * A1 * (1.0 + EB)
+    summed = inner + n2 * U * (S1 + inner)
+    return EB * ref.abs() + summed * (1.0 + EB)
+
+
+def ratios(got, ref, bnd):
+    """per element |got - ref| / bound: 0 where equal, inf for a non-finite result or an error over a zero bound"""
+    got, ref, bnd = got.detach().cpu().double(), ref.double(), bnd.double()
+    assert got.shape == ref.shape == bnd.shape, (got.shape, ref.shape, bnd.shape)
+    err = (got - ref).abs()
+    r = torch.where(err == 0, torch.zeros_like(err), err / bnd.clamp_min(1e-300))
+    return torch.where(torch.isfinite(r), r, torch.full_like(r, float("inf")))
+
+
+def worst_ratio(got, ref, bnd):
+    return float(ratios(got, ref, bnd).max()) if ref.numel() else 0.0
+
+
+def report(kernel, case, outputs):
+    """outputs: name -> worst ratio.  Prints `RATIO conv <kernel> <case> <output>=<worst |err| / bound> ...`, then asserts."""
+    print("RATIO conv %s %s %s" % (kernel, case, " ".join("%s=%.3f" % kv for kv in outputs.items())))
+    assert all(v <= 1.0 for v in outputs.values()), (kernel, case, outputs)
+
+
+def in_bf16_normal_range(ref):
+    a = ref.abs()
+    return bool(((a == 0) | ((a >= BF16_MIN_NORMAL) & (a <= BF16_MAX))).all())
+
+
+# ------------------------------------------------------------------ plans
+def nt_stages(bm, bn):
+    return {192: {256: 2, 192: 3, 128: 4}, 256: {192: 2, 128: 3}, 128: {256: 3, 128: 4}}.get(bn, {}).get(bm, 0)
+
+
+def gemm_plan(M, Ncol, K, ws_bytes, tile=None, splitk=0):
+    """gemm_plan.h's choose_tile / choose_splits for an implicit convolution, restated: (bm, bn, splits, kt_per_split)"""
+    if tile is not None:
+        bm, bn = tile
+    else:
+        bn = 192 if Ncol % 192 == 0 else 256 if (Ncol % 256 == 0 or Ncol > 1024) else 128
+        best, bm = -1.0, 128
+        for b, eff in ((256, 1.0), (192, 0.97), (128, 0.85)):
+            if not nt_stages(b, bn):
+                continue
+            tiles = -(-M // b) * -(-Ncol // bn)
+            sc = M * Ncol / (-(-tiles // 256) * 256.0 * b * bn) * eff
+            if sc > best:
+                best, bm = sc, b
+    tiles, nt = -(-M // bm) * -(-Ncol // bn), -(-K // 64)
+    if splitk >= 1:
+        S = splitk if (splitk <= nt and splitk * M * Ncol * 4 <= ws_bytes) else 1
+    elif tiles > 128 or nt < 8:
+        S = 1
+    else:
+        S = min(256 // tiles, nt // 4, 16)
+        while S > 1 and S * M * Ncol * 4 > ws_bytes:
+            S -= 1
+        S = max(S, 1)
+    kps = -(-nt // S)
+    return bm, bn, -(-nt // kps), kps
+
+
+def wgrad_plan(N, H, W, Cin, Cout):
+    """plan256 for the nine tap problems of one image, restated: (S, slab rows, 32-row stages per slab, reduce form)"""
+    Mp, tiles = N * (H + 2) * (W + 2), -(-Cout // 256) * -(-Cin // 256)
+    R = 32
+    while 9 * tiles * -(-Mp // R) > 256 and R < Mp:
+        R += 32
+    S = max(-(-Mp // R), 1)
+    slab = -(-(-(-Mp // S)) // 32) * 32            # the rows of a slab, ceil(Mp / S), rounded up to whole 32-row steps
+    form = "direct" if S == 1 else "lpq16" if (9 * Cout * Cin // 4 <= 32768 and S >= 16) else "lpq1"
+    return S, slab, slab // 32, form
+
+
+def wgrad_workspace_floats(S, Cin, Cout):
+    """ws_floats256 for those problems (the first carries the bias gradient): nothing when S = 1"""
+    return 0 if S == 1 else 9 * S * Cout * Cin + (S * Cout + 3) // 4 * 4
+
+
+def wgrad_multi_plan(levels, Cin, Cout):
+    """conv_multi_plan: (R, [slabs per image])"""
+    Ms, tiles = [n * (h + 2) * (w + 2) for n, h, w in levels], -(-Cout // 256) * -(-Cin // 256)
+    R = 32
+    while sum(9 * tiles * -(-m // R) for m in Ms) > 256 and R < max(Ms):
+        R += 32
+    return R, [-(-m // R) for m in Ms]
+
+
+# ------------------------------------------------------------------ layouts
+def pad_rows(N, H, W):
+    """dgx_conv3x3_pad_rows (gemm_nt.hip)"""
+    return N * (H + 2) * (W + 2) + 2 * (W + 3)
+
+
+def pad_grid(x):
+    """(N, H+2, W+2, C): x inside a zero border, in x's dtype"""
+    N, H, W, C = x.shape
+    g = x.new_zeros(N, H + 2, W + 2, C)
+    g[:, 1:H + 1, 1:W + 1] = x
+    return g
+
+
+def pad_layout(x):
+    """the zero-bordered copy as im2col.hip documents it: (W + 3) slack rows, the (N, H+2, W+2) grid, (W + 3) slack rows, of C elements"""
+    N, H, W, C = x.shape
+    s = x.new_zeros(W + 3, C)
+    return torch.cat([s, pad_grid(x).reshape(-1, C), s], 0)
+
+
+def flip_twin(w_ohwi):
+    """(Cin, 3, 3, Cout)[ci][ey][ex][co] = w[co][2-ey][2-ex][ci]: the operand of the input gradient"""
+    return w_ohwi.flip(1, 2).permute(3, 1, 2, 0).contiguous()
+
+
+def out_hw(H, W, stride, mutant=None):
+    if mutant == "half_out" and stride == 2:
+        return H // 2, W // 2
+    return (H - 1) // stride + 1, (W - 1) // stride + 1
+
+
+def _tap_rows(xf, N, H, W, stride, ky, kx, mutant, Ho, Wo):
+    """rows (N Ho Wo, C) that tap (ky, kx) reads, zero outside the image, by flat index arithmetic on the (N H W, C) matrix"""
+    n = torch.arange(N).view(N, 1, 1)
+    iy = (torch.arange(Ho) * stride - 1 + ky).view(1, Ho, 1)
+    ix = (torch.arange(Wo) * stride - 1 + kx).view(1, 1, Wo)
+    vy, vx = (iy >= 0) & (iy < H), (ix >= 0) & (ix < W)
+    flat = (n * H + iy) * W + ix
+    valid = (vy & vx).expand(N, Ho, Wo)
+    if mutant == "row_wrap":
+        valid = valid | (vy & (ix == -1) & (flat >= 0))
+    elif mutant == "image_wrap":
+        valid = valid | ((iy == -1) & vx & (flat >= 0))
+    if mutant == "corner_tap":
+        inward = H > 1 and W > 1          # the tap that points into the image; the centre tap on a one-pixel-wide map
+        oy, ox = torch.arange(Ho).view(1, Ho, 1), torch.arange(Wo).view(1, 1, Wo)
+        for a, ty in ((0, 2), (Ho - 1, 0)):
+            for b, tx in ((0, 2), (Wo - 1, 0)):
+                if (ky, kx) == ((ty, tx) if inward else (1, 1)):
+                    valid = valid & ~((oy == a) & (ox == b))
+    rows = xf[flat.clamp(0, N * H * W - 1).reshape(-1)]
+    return torch.where(valid.reshape(-1, 1), rows, torch.zeros_like(rows))          # +0 outside, a -0 inside stays -0
+
+
+def split_tail_tiles(kc, splits, kps):
+    """(tap, channel block) of the last K-tile of every split"""
+    nt = 9 * kc
+    return [divmod(min((s + 1) * kps, nt) - 1, kc) for s in range(splits)]
+
+
+# ------------------------------------------------------------------ forward / input gradient
+def conv_fwd64(x, w_ohwi, bias, relu, stride=1, mutant=None, plan=None):
+    """x (N, H, W, Cin), w (Cout, 3, 3, Cin), bias (Cout) or None -> y (N, Ho, Wo, Cout): 3x3, pad 1, stride 1 | 2.
+    plan (mutants only): (bm, bn, splits, kt_per_split) of the launch."""
+    N, H, W, Cin = x.shape
+    Cout = w_ohwi.shape[0]
+    Ho, Wo = out_hw(H, W, stride)
+    Hm, Wm = out_hw(H, W, stride, mutant)
+    xf, w = x.double().reshape(-1, Cin), w_ohwi.double().clone()
+    if mutant == "chunk8":
+        w[:, 2, 2, Cin - 8:] = 0
+    if mutant == "split_tail":
+        for tap, blk in split_tail_tiles(Cin // 64, plan[2], plan[3]):
+            w[:, tap // 3, tap % 3, 64 * blk:64 * blk + 64] = 0
+    acc, A = torch.zeros(N * Hm * Wm, Cout, dtype=F64), torch.zeros(N * Hm * Wm, Cout, dtype=F64)
+    for ky in range(3):
+        for kx in range(3):
+            wt = w[:, kx, ky] if mutant == "taps_transposed" else w[:, 2 - ky, 2 - kx] if mutant == "taps_flipped" else w[:, ky, kx]
+            rows = _tap_rows(xf, N, H, W, stride, ky, kx, mutant, Hm, Wm)
+            acc += rows @ wt.t()
+            A += rows.abs() @ wt.abs().t()
+    if (Hm, Wm) != (Ho, Wo):           # a kernel with the wrong output grid writes its rows back to back into the buffer
+        full = torch.zeros(N * Ho * Wo, Cout, dtype=F64)
+        full[:acc.shape[0]] = acc
+        acc, A = full, torch.zeros_like(full)
+    n = 9 * Cin
+    if bias is not None:
+        b = bias.double()
+        n += 1
+        A = A + b.abs()
+        if mutant == "relu_first" and relu:
+            acc = acc.clamp_min(0)
+        acc = acc + b * (plan[2] if mutant == "bias_per_split" else 1)
+    if relu and mutant != "relu_first":
+        acc = acc.clamp_min(0)
+    if mutant == "row_tail":
+        acc[acc.shape[0] // plan[0] * plan[0]:] = 0
+    if mutant == "col_tail":
+        acc[:, Cout // 256 * 256:] = 0
+    return acc.view(N, Ho, Wo, Cout), A.view(N, Ho, Wo, Cout), n
+
+
+def relu_mask(dy, y_kernel):
+    """dy where the kernel's own saved bf16 activation is > 0 (-0 and +0 are not), else 0"""
+    return dy if y_kernel is None else dy * (y_kernel.float() > 0).to(dy.dtype)
+
+
+def conv_dgrad64(dy, w_ohwi, y_kernel, relu, mutant=None, plan=None):
+    """dx (N, H, W, Cin) of the stride-1 convolution: the forward restatement over the masked dy and the tap-flipped twin.  n counts the
+    whole K-tiles of the kernel's contraction (Cout rounded up to 64: the Python layer pads with zero channels)."""
+    g = relu_mask(dy.double(), y_kernel if relu else None)
+    ref, A, _ = conv_fwd64(g, flip_twin(w_ohwi), None, False, mutant=mutant, plan=plan)
+    return ref, A, 9 * (-(-w_ohwi.shape[0] // 64) * 64)
+
+
+# ------------------------------------------------------------------ weight / bias gradient
+def conv_wgrad64(dy, x, g0, beta, mutant=None, plan=None):
+    """dy (N, H, W, Cout) (already masked), x (N, H, W, Cin), g0 = (gw0 (Cout, 3, 3, Cin), gb0 (Cout)) or None -> ((dW, db), (A_w, A_b), n):
+    the nine tap problems over the padded grid, dW[co][tap][ci] = beta gw0 + sum_m dypad[m][co] xpad[m + shift(tap)][ci].
+    plan (mutants only): (S, slab rows)."""
+    N, H, W, Cout = dy.shape
+    Cin, wp, Mp = x.shape[3], W + 2, N * (H + 2) * (W + 2)
+    if mutant == "border_counted":
+        g = dy.double()
+        g = torch.cat([g[:, :1], g, g[:, -1:]], 1)
+        dyp = torch.cat([g[:, :, :1], g, g[:, :, -1:]], 2).reshape(Mp, Cout)
+    else:
+        dyp = pad_grid(dy.double()).reshape(Mp, Cout)
+    xp = pad_layout(x.double())
+    keep = torch.ones(Mp, 1, dtype=F64)
+    if mutant == "step_tail":
+        S, slab = plan
+        for s in range(S):
+            end = min(Mp, (s + 1) * slab)
+            keep[s * slab + (end - s * slab) // 32 * 32:end] = 0
+    if mutant == "last_slab":
+        keep[(plan[0] - 1) * plan[1]:] = 0
+    dW, Aw = torch.zeros(Cout, 3, 3, Cin, dtype=F64), torch.zeros(Cout, 3, 3, Cin, dtype=F64)
+    dk = dyp * keep
+    for t in range(9):
+        xs = xp[(t // 3) * wp + t % 3:(t // 3) * wp + t % 3 + Mp]
+        ky, kx = (t % 3, t // 3) if mutant == "taps_transposed" else (t // 3, t % 3)
+        dW[:, ky, kx] = dk.t() @ xs
+        Aw[:, ky, kx] = dk.abs().t() @ xs.abs()
+    if mutant == "db_tap4_shift":
+        flat = torch.cat([pad_layout(dy.double()).reshape(-1), torch.zeros(Mp * max(Cin, Cout), dtype=F64)])
+        db = flat[(wp + 1) * Cin:(wp + 1) * Cin + Mp * Cout].view(Mp, Cout).sum(0)
+    else:
+        db = dk.sum(0)
+    Ab = dk.abs().sum(0)
+    n = Mp
+    if beta != 0.0:
+        gw0, gb0 = g0[0].double(), g0[1].double()
+        n += 1
+        Aw, Ab = Aw + abs(beta) * gw0.abs(), Ab + abs(beta) * gb0.abs()
+        if mutant != "beta_ignored":
+            k = plan[0] if mutant == "beta_per_slab" else 1
+            dW, db = dW + k * beta * gw0, db + k * beta * gb0
+    return (dW, db), (Aw, Ab), n
+
+
+# ------------------------------------------------------------------ column-matrix form
+def im2col64(x, stride):
+    """col[(n, oy, ox)][(ky*3 + kx) C + c] = x[n][oy s - 1 + ky][ox s - 1 + kx][c], 0 outside: exact, in x's dtype"""
+    N, H, W, C = x.shape
+    Ho, Wo = out_hw(H, W, stride)
+    xf = x.reshape(-1, C)
+    return torch.cat([_tap_rows(xf, N, H, W, stride, t // 3, t % 3, None, Ho, Wo) for t in range(9)], 1)
+
+
+def col2im64(dcol, N, H, W, C, stride, mutant=None):
+    """dx[n][y][x][c] = sum over the <= 9 (ky, kx, oy, ox) that read (y, x) of dcol[(n, oy, ox)][(ky*3 + kx) C + c] -> (ref, A, n):
+    n = the number of addends of each element"""
+    Ho, Wo = out_hw(H, W, stride, mutant)
+    d = dcol.double().reshape(-1)[:N * Ho * Wo * 9 * C].view(N, Ho, Wo, 9, C)
+    ref, A, cnt = (torch.zeros(N, H, W, C, dtype=F64) for _ in range(3))
+    yy, xx = torch.arange(H), torch.arange(W)
+    for ky in range(3):
+        ty = yy - ky if mutant == "parity" else yy + 1 - ky
+        oky = (ty >= 0) & (ty % stride == 0) & (ty // stride < Ho)
+        for kx in range(3):
+            tx = xx - kx if mutant == "parity" else xx + 1 - kx
+            okx = (tx >= 0) & (tx % stride == 0) & (tx // stride < Wo)
+            ys, xs = yy[oky], xx[okx]
+            if ys.numel() == 0 or xs.numel() == 0:
+                continue
+            v = d[:, (ty[oky] // stride)][:, :, (tx[okx] // stride)][:, :, :, ky * 3 + kx]
+            iy, ix = ys.view(-1, 1).expand(-1, xs.numel()), xs.view(1, -1).expand(ys.numel(), -1)
+            ref[:, iy, ix] += v
+            A[:, iy, ix] += v.abs()
+            cnt[:, iy, ix] += 1
+    return ref, A, cnt
+
+
+def conv_dgrad_cols64(dy, w_ohwi, N, H, W, stride):
+    """The column-matrix input gradient of the Python layer (GEMM to a bf16 dcol, then col2im): (ref, A1, S1, n1, cnt) for
+    `two_rounding_bound`: dcol[(m)][(tap, ci)] = sum_co dy[m][co] w[co][tap][ci]."""
+    Cout, Cin = w_ohwi.shape[0], w_ohwi.shape[3]
+    g, wm = dy.double().reshape(-1, Cout), w_ohwi.double().reshape(Cout, 9 * Cin)
+    dcol, acol = g @ wm, g.abs() @ wm.abs()
+    ref, S1, cnt = col2im64(dcol, N, H, W, Cin, stride)
+    A1 = col2im64(acol, N, H, W, Cin, stride)[0]
+    return ref, A1, S1, Cout, cnt
+
+
+def conv_wgrad_cols64(dy, x, stride):
+    """The column-matrix weight / bias gradient (stride 1 | 2): dW[co][tap][ci] = sum_m dy[m][co] col[m][(tap, ci)] over the N Ho Wo
+    output pixels -> ((dW (Cout, 3, 3, Cin), db), (A_w, A_b), n)"""
+    Cout, Cin = dy.shape[3], x.shape[3]
+    g, col = dy.double().reshape(-1, Cout), im2col64(x, stride).double()
+    return ((g.t() @ col).view(Cout, 3, 3, Cin), g.sum(0)), ((g.abs().t() @ col.abs()).view(Cout, 3, 3, Cin), g.abs().sum(0)), g.shape[0]
+
+
+# ------------------------------------------------------------------ ConvTranspose2d(2, 2)
+def deconv_shuffle(y2, N, H, W, Cout):
+    """out[n][2h+dy][2w+dx][co] = y2[(n, h, w)][4 co + 2 dy + dx]"""
+    return y2.view(N, H, W, Cout, 2, 2).permute(0, 1, 4, 2, 5, 3).reshape(N, 2 * H, 2 * W, Cout)
+
+
+def deconv_unshuffle(gy, N, H, W, Cout):
+    return gy.view(N, H, 2, W, 2, Cout).permute(0, 1, 3, 5, 2, 4).reshape(N * H * W, 4 * Cout)
+
+
+def deconv2x2_64(x, w, bias, relu, dy=None, y_kernel=None):
+    """x (N, H, W, Cin), w (Cin, Cout, 2, 2) read as the stored matrix (Cin, Cout * 4), bias (Cout) -> dict of (ref, A, n):
+    "y" (N, 2H, 2W, Cout); with dy (same shape; y_kernel = the layer's own ReLU-ed output when relu): "dx", "dw" (Cin, Cout, 2, 2), "db"."""
+    N, H, W, Cin = x.shape
+    Cout = w.shape[1]
+    x2, wm = x.double().reshape(-1, Cin), w.double().reshape(Cin, 4 * Cout)
+    y2, A2 = x2 @ wm, x2.abs() @ wm.abs()
+    n = Cin
+    if bias is not None:
+        b4 = bias.double().repeat_interleave(4)
+        y2, A2, n = y2 + b4, A2 + b4.abs(), n + 1
+    if relu:
+        y2 = y2.clamp_min(0)
+    out = {"y": (deconv_shuffle(y2, N, H, W, Cout), deconv_shuffle(A2, N, H, W, Cout), n)}
+    if dy is not None:
+        g2 = deconv_unshuffle(relu_mask(dy.double(), y_kernel if relu else None).contiguous(), N, H, W, Cout)
+        out["dx"] = ((g2 @ wm.t()).view(N, H, W, Cin), (g2.abs() @ wm.abs().t()).view(N, H, W, Cin), 4 * Cout)
+        out["dw"] = ((x2.t() @ g2).view(Cin, Cout, 2, 2), (x2.abs().t() @ g2.abs()).view(Cin, Cout, 2, 2), N * H * W)
+        out["db"] = (g2.sum(0).view(Cout, 4).sum(1), g2.abs().sum(0).view(Cout, 4).sum(1), 4 * N * H * W)
+    return out
+
+
+# ------------------------------------------------------------------ inputs
+def bf(t):
+    return t.to(BF16)
+
+
+def plant_zeros(t, gen):
+    """exact zeros on about half of the elements, every other one of them -0"""
+    z = torch.rand(t.shape, generator=gen) < 0.5
+    neg = z & (torch.rand(t.shape, generator=gen) < 0.5)
+    t = torch.where(z, torch.zeros_like(t), t)
+    return torch.where(neg, -torch.zeros_like(t), t)
+
+
+def make_inputs(kind, geom, seed):
+    """bf16 x (N, H, W, Cin), w (Cout, 3, 3, Cin), bias (Cout), dy (N, H, W, Cout), saved activation ysave (N, H, W, Cout), and fp32
+    g0 = (gw0, gb0) of one geometry.
+      ordinary    randn, weights * 0.05
+      cancelling  x + 64 against mixed-sign weights (and dy + 64 for the weight gradient's bias column): A >> |ref|
+      postrelu    exact zeros and -0 in x and in the saved activation"""
+    N, H, W, Cin, Cout = geom
+    gen = torch.Generator().manual_seed(seed)
+    x = torch.randn(N, H, W, Cin, generator=gen)
+    w = torch.randn(Cout, 3, 3, Cin, generator=gen) * 0.05
+    bias = torch.randn(Cout, generator=gen)
+    dy = torch.randn(N, H, W, Cout, generator=gen)
+    ysave = torch.randn(N, H, W, Cout, generator=gen)
+    if kind == "cancelling":
+        x = x + 64.0
+    elif kind == "postrelu":
+        x = plant_zeros(x.clamp_min(0), gen)
+        ysave = plant_zeros(ysave.clamp_min(0), gen)
+    else:
+        assert kind == "ordinary", kind
+    g0 = (torch.randn(Cout, 3, 3, Cin, generator=gen), torch.randn(Cout, generator=gen))
+    return {"x": bf(x), "w": bf(w), "bias": bf(bias), "dy": bf(dy), "ysave": bf(ysave), "g0": g0}
+
+
+def seed_of(geom, kind):
+    return 1000 * sum((i + 1) * v for i, v in enumerate(geom)) + INPUT_KINDS.index(kind)
