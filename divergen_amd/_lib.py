@@ -162,6 +162,11 @@ SIGNATURES = {
     "dgx_paste_rle": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
     "dgx_rle_encode": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     "dgx_rle_to_string": (c_i64, [c_p, c_i64, c_p, c_i64]),
+    "dgx_rle_from_string": (c_i64, [c_p, c_p, c_i64, c_p, c_i64, c_p]),
+    "dgx_rle_iou": (c_i, [c_p] * 11 + [c_i64, c_i64, c_p, c_p]),
+    "dgx_box_iou_xywh_f64": (c_i, [c_p] * 5 + [c_i64, c_i64, c_p, c_p]),
+    "dgx_lvis_match": (c_i, [c_p] * 4 + [c_i64] * 3 + [c_p] * 6 + [c_i, c_p, c_i, c_p, c_i64, c_p, c_p, c_p]),
+    "dgx_lvis_accumulate": (c_i, [c_p, c_p, c_i64, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
     "dgx_grad_bank_update": (c_i, [c_p, c_p, c_i64, c_f, c_f, c_p]),
     "dgx_grad_sim_workspace_bytes": (c_i64, [c_i64]),
     "dgx_grad_sim": (c_i, [c_p, c_p, c_i64, c_p, c_p, c_p, c_p]),

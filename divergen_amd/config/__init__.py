@@ -185,6 +185,11 @@ def get_cfg():
     #   SOLVER.ALLREDUCE_DTYPE: "fp32" (the reference's DDP: gradients all-reduced as they are) or "bf16" (gradient buckets go over
     #   xGMI as bf16, half the bytes per step; engine/ddp.py ArenaReducer(wire_dtype=...)).
     cfg.SOLVER.ALLREDUCE_DTYPE = "fp32"
+    #   TEST.LVIS_EVAL_DEVICE: LVISEvaluator scores the gathered detections on the GPU (evaluation/lvis_eval_device.py: mask / box IoU,
+    #   greedy matching and the precision / recall curves as kernels of divergen_amd/csrc/lvis_eval.hip, bit for bit what the Python
+    #   evaluator computes) instead of in evaluation/lvis_eval.py.  Off by default: the Python evaluator stays the path, and the device
+    #   module is not even imported.
+    cfg.TEST.LVIS_EVAL_DEVICE = False
     return cfg
 
 

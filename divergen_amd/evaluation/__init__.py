@@ -39,11 +39,17 @@ def instances_to_coco_json(instances, img_id):
 class LVISEvaluator:
     """LVISEvaluator (D2/evaluation/lvis_evaluation.py:22-178): collects per-image results like LVISResultsWriter and, when the
     split's annotation json is available, scores them -- box AP and mask AP with the r / c / f breakdown -- with this build's
-    restatement of lvis-api's LVISEval (evaluation/lvis_eval.py).  `evaluate()` returns {"bbox": {...}, "segm": {...}}."""
+    restatement of lvis-api's LVISEval (evaluation/lvis_eval.py), or, with TEST.LVIS_EVAL_DEVICE / device_eval=True, with the same
+    arithmetic on the GPU (evaluation/lvis_eval_device.py).  `evaluate()` returns {"bbox": {...}, "segm": {...}}."""
 
-    def __init__(self, dataset_name, cfg=None, distributed=True, output_dir=None, max_dets_per_image=300, tasks=("bbox", "segm")):
+    def __init__(self, dataset_name, cfg=None, distributed=True, output_dir=None, max_dets_per_image=300, tasks=("bbox", "segm"),
+                 device_eval=None):
         from ..data.build import dataset_files
         self._json, _ = dataset_files(dataset_name)
+        # device_eval: score on the GPU (evaluation/lvis_eval_device.py); None reads TEST.LVIS_EVAL_DEVICE of cfg
+        if device_eval is None:
+            device_eval = bool(cfg.TEST.get("LVIS_EVAL_DEVICE", False)) if cfg is not None else False
+        self._device_eval = bool(device_eval)
         self._writer = LVISResultsWriter(output_dir, distributed)
         self._max_dets, self._tasks = max_dets_per_image, tasks
         if cfg is not None and not cfg.MODEL.MASK_ON:
@@ -60,6 +66,8 @@ class LVISEvaluator:
         from collections import OrderedDict
         from ..utils import comm
         from .lvis_eval import evaluate_predictions_on_lvis
+        if self._device_eval:
+            from .lvis_eval_device import evaluate_predictions_on_lvis_device as evaluate_predictions_on_lvis
         if self._writer.evaluate() is None or not comm.is_main_process():
             return {}
         results = getattr(self._writer, "results", [])

@@ -913,6 +913,51 @@ int dgx_rle_encode(const uint8_t* bits, int32_t* counts, int32_t* nruns, int N, 
 int64_t dgx_rle_to_string(const int32_t* counts, int64_t n, char* out, int64_t cap);
 
 /* ---------------------------------------------------------------------------------------------
+ * LVIS AP scoring on the device (csrc/lvis_eval.hip; opt-in with TEST.LVIS_EVAL_DEVICE): the arithmetic of
+ * divergen_amd/evaluation/lvis_eval.py (lvis-api's LVISEval, what D2/evaluation/lvis_evaluation.py:331-380 calls), bit for bit.
+ *
+ * Group structure shared by the four kernels: group g = one (image, category) with D_g detections and G_g ground truths,
+ *   d_off, g_off, iou_off i64 (n_groups + 1): detections d_off[g] .. d_off[g+1], ground truths g_off[g] .. g_off[g+1] of flat
+ *   per-detection / per-ground-truth arrays; its IoUs are out[iou_off[g] + d * G_g + j], iou_off[g+1] - iou_off[g] = D_g * G_g.
+ *   The detections of a group stand in the order the matcher visits them (descending score, stable).
+ *
+ * HOST function, the inverse of the string writer above (maskApi.c rleFrString), batched: string i is buf[off[i]] ..
+ * buf[off[i+1]]; its run lengths are counts[count_off[i]] .. counts[count_off[i+1]].  count_off (n + 1) is always written;
+ * counts only when all of them fit `cap`.  Returns the number of run lengths, or -(needed) if cap is too small (call with
+ * cap 0 for the size).  A run length is a 64-bit value: at most 12 characters each. */
+int64_t dgx_rle_from_string(const char* buf, const int64_t* off, int64_t n, int64_t* counts, int64_t cap, int64_t* count_off);
+/* Mask IoU (maskApi.c rleIou, iscrowd = 0) of every (detection, ground truth) pair of every group.  A mask is its foreground
+ * runs over the column-major pixel index (H*W < 2^31): start i32, end i32 (exclusive), cum i32 = foreground pixels up to and
+ * including the run; mask m owns runs run_off[m] .. run_off[m+1] (i64, one entry more than masks).  The d_* arrays hold the
+ * detections' masks, the g_* arrays the ground truths'.  n_pairs = iou_off[n_groups].  Intersection and union are 64-bit integers,
+ * out f64 = (double)inter / (double)union, 0 when the union is 0. */
+int dgx_rle_iou(const int32_t* d_start, const int32_t* d_end, const int32_t* d_cum, const int64_t* d_run_off,
+                const int32_t* g_start, const int32_t* g_end, const int32_t* g_cum, const int64_t* g_run_off,
+                const int64_t* d_off, const int64_t* g_off, const int64_t* iou_off, int64_t n_groups, int64_t n_pairs,
+                double* out, void* stream);
+/* Box IoU (lvis_eval.box_iou_xywh) in float64, no contraction: d_box f64 (sum D, 4), g_box f64 (sum G, 4), XYWH. */
+int dgx_box_iou_xywh_f64(const double* d_box, const double* g_box, const int64_t* d_off, const int64_t* g_off,
+                         const int64_t* iou_off, int64_t n_groups, int64_t n_pairs, double* out, void* stream);
+/* LVISEval._evaluate_img for every group x area range x IoU threshold.
+ *   ious f64 as written by the two functions above;  gt_area f64, gt_ignore u8, gt_id i64 per ground truth;
+ *   dt_area f64, dt_nel u8 (the category is in not_exhaustive_category_ids of the image) per detection;
+ *   iou_thrs f64 (T);  area_rng f64 (A, 2);  n_dt = d_off[n_groups], n_gt = g_off[n_groups];
+ *   workspace: A * T * n_gt bytes (the matched flags of the ground truths; cleared here);
+ *   dt_match i64 (A, T, n_dt): id of the matched ground truth, 0 = none;  dt_ignore u8 (A, T, n_dt). */
+int dgx_lvis_match(const double* ious, const int64_t* d_off, const int64_t* g_off, const int64_t* iou_off, int64_t n_groups,
+                   int64_t n_dt, int64_t n_gt, const double* gt_area, const uint8_t* gt_ignore, const int64_t* gt_id,
+                   const double* dt_area, const uint8_t* dt_nel, const double* iou_thrs, int T, const double* area_rng,
+                   int A, uint8_t* workspace, int64_t workspace_bytes, int64_t* dt_match, uint8_t* dt_ignore, void* stream);
+/* The precision / recall curves of LVISEval.run per (category, area range, threshold).
+ *   dt_matched, dt_ignore u8 (A, T, n_dt);  order i64: position p of category k (cat_off[k] <= p < cat_off[k+1], cat_off i64
+ *   (K + 1)) reads detection order[p] -- the category's detections by descending score, stable over ascending image id;
+ *   num_gt i64 (K, A): unignored ground truths (0: the entries are left as they are, the caller filled them with -1);
+ *   rec_thrs f64 (R <= 1024);  precision f64 (T, R, K, A);  recall f64 (T, K, A). */
+int dgx_lvis_accumulate(const uint8_t* dt_matched, const uint8_t* dt_ignore, int64_t n_dt, const int64_t* order,
+                        const int64_t* cat_off, int K, const int64_t* num_gt, const double* rec_thrs, int R, int T, int A,
+                        double* precision, double* recall, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * BSGAL gain scoring on flat gradient arenas (BS/bsgal/modeling/meta_arch/custom_rcnn.py).
  * dgx_grad_bank_update replaces update_grad_bank (:1046-1062): bank = bank * a + grad * b in that fp32 order
  *   ("AVERAGE": a = it/(it+1), b = 1/(it+1);  "MOMENTUMm": a = m, b = 1 - m).  bank, grad: f32 (n), 16-byte aligned.
