@@ -242,7 +242,7 @@ __global__ __launch_bounds__(256) void cn_head_outputs_bwd_kernel(HoLevels P, co
         *reinterpret_cast<u32x4*>(P.dx[l] + r * P.C + 8 * ch) = o;
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ds += __shfl_xor(ds, o);
+    for (int o = 32; o > 0; o >>= 1) ds += __shfl_xor(ds, o);      // (through wave_sum this kernel comes out one VGPR larger)
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ds;
     __syncthreads();
     if (threadIdx.x == 0) part[(int64_t)l * max_blocks + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
@@ -253,8 +253,7 @@ __global__ __launch_bounds__(64) void cn_head_scale_grad_kernel(HoLevels P, cons
     const int nb = (int)(((int64_t)P.rows[l] * (P.C >> 3) + 255) / 256);
     float s = 0.f;
     for (int b = threadIdx.x; b < nb; b += 64) s += part[(int64_t)l * max_blocks + b];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    s = wave_sum(s);
     if (threadIdx.x == 0) d_scale[l] = s;
 }
 

@@ -115,9 +115,7 @@ __global__ __launch_bounds__(256) void detic_fold_kernel(const float* __restrict
 #pragma unroll
         for (int k = 0; k < NPART; ++k) a[k] += part[(int64_t)r * NPART + k];
 #pragma unroll
-    for (int k = 0; k < NPART; ++k)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a[k] += __shfl_xor(a[k], o);
+    for (int k = 0; k < NPART; ++k) a[k] = wave_sum(a[k]);
     if ((threadIdx.x & 63) == 0)
 #pragma unroll
         for (int k = 0; k < NPART; ++k) red[threadIdx.x >> 6][k] = a[k];

@@ -22,6 +22,63 @@ __device__ __forceinline__ uint32_t pack_bf2(float lo, float hi) {
 }
 __device__ __forceinline__ uint16_t f2bf(float f) { return (uint16_t)pack_bf2(f, 0.f); }
 
+// ---- rows of fp32 / bf16 (uint16_t) storage as fp32: 4 elements (a quad) or 8 (a 16-byte bf16 chunk) per lane ----
+// a quad as loaded (kept packed in registers: 2 registers for bf16, 4 for fp32) and its fp32 expansion
+template <typename T> struct Raw4;
+template <> struct Raw4<float> {
+    typedef float4 type;
+    static __device__ __forceinline__ float4 ld(const float* row, int i) { return reinterpret_cast<const float4*>(row)[i]; }
+    static __device__ __forceinline__ float4 f(float4 r) { return r; }
+    static __device__ __forceinline__ float4 zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+};
+template <> struct Raw4<uint16_t> {
+    typedef uint2 type;
+    static __device__ __forceinline__ uint2 ld(const uint16_t* row, int i) { return reinterpret_cast<const uint2*>(row)[i]; }
+    static __device__ __forceinline__ float4 f(uint2 d) {
+        return make_float4(__uint_as_float(d.x << 16), __uint_as_float(d.x & 0xffff0000u), __uint_as_float(d.y << 16), __uint_as_float(d.y & 0xffff0000u));
+    }
+    static __device__ __forceinline__ uint2 zero() { return make_uint2(0u, 0u); }
+};
+// quad i of a row
+template <typename T> __device__ __forceinline__ float4 ld4(const T* row, int i) { return Raw4<T>::f(Raw4<T>::ld(row, i)); }
+__device__ __forceinline__ void st4(float* row, int i, float4 v) { reinterpret_cast<float4*>(row)[i] = v; }
+__device__ __forceinline__ void st4(uint16_t* row, int i, float4 v) {
+    reinterpret_cast<uint2*>(row)[i] = make_uint2(pack_bf2(v.x, v.y), pack_bf2(v.z, v.w));
+}
+// v as it reads back after a store in type T
+template <typename T> __device__ __forceinline__ float4 rnd4(float4 v) {
+    if constexpr (sizeof(T) == 4) return v;
+    else return Raw4<uint16_t>::f(make_uint2(pack_bf2(v.x, v.y), pack_bf2(v.z, v.w)));
+}
+
+// 8 bf16 in a 16-byte register quad V (u32x4, or HIP's uint4 where a kernel's pointers are typed so) <-> 8 floats
+template <class V> __device__ __forceinline__ void unpack8(const V r, float (&v)[8]) {
+    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { v[2 * i] = __uint_as_float(w[i] << 16); v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
+}
+template <class V = u32x4> __device__ __forceinline__ V pack8(const float (&v)[8]) {
+    return V{pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7])};
+}
+// the 8 elements at p (16-byte aligned)
+__device__ __forceinline__ void ld8(const uint16_t* p, float (&v)[8]) { unpack8(*reinterpret_cast<const uint4*>(p), v); }
+__device__ __forceinline__ void ld8(const float* p, float (&v)[8]) {
+    const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+__device__ __forceinline__ void st8(uint16_t* p, const float (&v)[8]) { *reinterpret_cast<uint4*>(p) = pack8<uint4>(v); }
+__device__ __forceinline__ void st8(float* p, const float (&v)[8]) {
+    reinterpret_cast<float4*>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
+    reinterpret_cast<float4*>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
+}
+
+// sum over the 64 lanes, in every lane: xor butterfly 32, 16, .., 1 (the order is part of every result that uses it)
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
 // D(16x16) += A(16x32) * B(32x16); lane l: a = A[l&15][slot (l>>4, 0..7)], b = B[slot][l&15],
 // d[r] = D[(l>>4)*4 + r][l&15].  A and B use the same (lane-group, i) -> k slot map.
 __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {

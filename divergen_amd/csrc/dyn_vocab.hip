@@ -198,8 +198,7 @@ __global__ __launch_bounds__(256) void zs_gather_kernel(const float* __restrict_
             ss += v * v;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+    ss = wave_sum(ss);
     if (lane == 0) red[w] = ss;
     __syncthreads();
     const float denom = fmaxf(sqrtf((red[0] + red[1]) + (red[2] + red[3])), 1e-12f);       // F.normalize: x / max(||x||, eps)

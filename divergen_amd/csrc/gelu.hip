@@ -6,13 +6,6 @@
 #include "dgx_common.h"
 
 namespace {
-__device__ __forceinline__ void unpack8g(const u32x4 r, float (&v)[8]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { v[2 * i] = __uint_as_float(r[i] << 16); v[2 * i + 1] = __uint_as_float(r[i] & 0xffff0000u); }
-}
-__device__ __forceinline__ u32x4 pack8g(const float (&v)[8]) {
-    return u32x4{pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7])};
-}
 constexpr float kInvSqrt2 = 0.70710678118654752440f;
 constexpr float kInvSqrt2Pi = 0.39894228040143267794f;
 }  // namespace
@@ -20,10 +13,10 @@ constexpr float kInvSqrt2Pi = 0.39894228040143267794f;
 __global__ __launch_bounds__(256) void gelu_fwd_kernel(const u32x4* __restrict__ x, u32x4* __restrict__ y, int64_t n8) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
         float v[8], o[8];
-        unpack8g(x[i], v);
+        unpack8(x[i], v);
 #pragma unroll
         for (int k = 0; k < 8; ++k) o[k] = 0.5f * v[k] * (1.0f + erff(v[k] * kInvSqrt2));
-        y[i] = pack8g(o);
+        y[i] = pack8(o);
     }
 }
 
@@ -40,15 +33,15 @@ __global__ __launch_bounds__(256) void gelu_bwd_colsum_kernel(const uint16_t* __
         for (int r = r0 + w; r < r1; r += 4) {
             const int64_t o = (int64_t)r * N + c0;
             float g[8], v[8], d[8];
-            unpack8g(*reinterpret_cast<const u32x4*>(dy + o), g);
-            unpack8g(*reinterpret_cast<const u32x4*>(x + o), v);
+            unpack8(*reinterpret_cast<const u32x4*>(dy + o), g);
+            unpack8(*reinterpret_cast<const u32x4*>(x + o), v);
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const float cdf = 0.5f * (1.0f + erff(v[k] * kInvSqrt2));
                 const float pdf = __expf(-0.5f * v[k] * v[k]) * kInvSqrt2Pi;
                 d[k] = g[k] * (cdf + v[k] * pdf);
             }
-            const u32x4 pk = pack8g(d);
+            const u32x4 pk = pack8(d);
             *reinterpret_cast<u32x4*>(dx + o) = pk;
             // the bias gradient sums the bf16-ROUNDED dx (what a separate pass over dx would read)
 #pragma unroll

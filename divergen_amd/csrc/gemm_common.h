@@ -9,12 +9,11 @@
 #include "winmap.h"
 #include <type_traits>
 
+constexpr int G_ORDERS = WM_IDENTITY | WM_CLASSIC | WM_COMPACT;      // the row orders of the residual epilogue (M rows, all of them tokens or classic rows)
 constexpr int GBK = 64;                 // K-step (elements): 128-byte tile rows
 static constexpr uint32_t G_OOB = 0x80000000u; // voffset beyond num_records: the lane's 16 bytes land in LDS as zeros
 
 namespace dgxgemm {
-struct GMap { int B, H, W, ws, shift, nWh, nWw, compact; };   // residual.hip's RMap; compact: winmap.h
-
 struct GemmP {
     const uint16_t* A;
     const uint16_t* B;
@@ -33,7 +32,7 @@ struct GemmP {
     void* out;              //         out = res + scale[b] * y
     const float* scale;     //         per-sample DropPath factor or null
     int res_dtype;
-    GMap map;
+    WmMap map;              //         the order of the GEMM rows (winmap.h)
     // implicit 3x3 convolution (pad 1, stride 1) over a zero-bordered NHWC image (dgx_conv3x3_*): K-tile kt of the A operand
     // is tap kt / conv_kc, channels 64 (kt % conv_kc) ..: the SAME rows shifted by (tap / 3) * conv_wp + tap % 3 pixels;
     // GEMM rows are the N*H*W OUTPUT pixels (cmap: n, h, w); row m reads the padded position of its pixel (per-lane offset), so
@@ -50,7 +49,6 @@ struct GemmP {
 };
 constexpr int GEMM_MAXG = 6;
 }  // namespace dgxgemm
-using dgxgemm::GMap;
 using dgxgemm::GemmP;
 
 namespace {
@@ -138,35 +136,6 @@ __device__ __forceinline__ void g_bias4(const u32x2 raw, float (&bv)[4]) {
 
 constexpr float kGInvSqrt2 = 0.70710678118654752440f;
 constexpr float kGInvSqrt2Pi = 0.39894228040143267794f;
-__device__ __forceinline__ void g_unpack8(const u32x4 r, float (&v)[8]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { v[2 * i] = __uint_as_float(r[i] << 16); v[2 * i + 1] = __uint_as_float(r[i] & 0xffff0000u); }
-}
-__device__ __forceinline__ u32x4 g_pack8(const float (&v)[8]) {
-    return u32x4{pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7])};
-}
-
-// window-order output row -> token index of the (B, H*W) stream, -1 for a padding row (residual.hip: residual_bwd_kernel)
-__device__ __forceinline__ int64_t g_row_token(const GMap& m, int64_t orow, int& b) {
-    if (m.ws == 0) {
-        b = (int)(orow / ((int64_t)m.H * m.W));
-        return orow;
-    }
-    if (m.compact) return wm_token_of_row(wm_geom(m.H, m.W, m.ws, m.shift), (int)orow, b);      // every compact row is a real token
-    const int Nw = m.ws * m.ws;
-    const int n = (int)(orow % Nw);
-    int64_t t = orow / Nw;
-    const int wc = (int)(t % m.nWw);
-    t /= m.nWw;
-    const int wr = (int)(t % m.nWh);
-    b = (int)(t / m.nWh);
-    int hh = wr * m.ws + n / m.ws + m.shift, ww = wc * m.ws + n % m.ws + m.shift;
-    const int Hp = m.nWh * m.ws, Wp = m.nWw * m.ws;
-    if (hh >= Hp) hh -= Hp;
-    if (ww >= Wp) ww -= Wp;
-    return (hh < m.H && ww < m.W) ? ((int64_t)b * m.H + hh) * m.W + ww : -1;
-}
-
 // Mode 3: (token << 32 | DropPath factor bits) of tile row `tid` (rows m0 ..) into the tile's LDS table, -1 for a padding row or one
 // beyond M.  The factor is fetched HERE, once per tile row -- as a load inside the read-out's `locate` it sat in front of every chunk's
 // store behind an s_waitcnt vmcnt(0) that also waited for the prefetched operands of the next slab and for the stores before it
@@ -174,7 +143,7 @@ __device__ __forceinline__ int64_t g_row_token(const GMap& m, int64_t orow, int&
 __device__ __forceinline__ void g_fill_rowtok(const GemmP& P, DGX_LDS int64_t* rowtok, int m0, int tid) {
     int b = 0;
     const int64_t orow = (int64_t)m0 + tid;
-    const int64_t tok = orow < P.M ? g_row_token(P.map, orow, b) : -1;
+    const int64_t tok = orow < P.M ? wm_row_token<int64_t, G_ORDERS>(P.map, orow, b) : -1;
     const float scv = (tok >= 0 && P.scale) ? P.scale[b] : 1.0f;
     rowtok[tid] = tok < 0 ? -1 : ((tok << 32) | (int64_t)__float_as_uint(scv));
 }
@@ -270,23 +239,23 @@ __device__ __forceinline__ void g_epi_finish(const GemmP& P, int gm, int gn, con
     } else if (P.mode == 2) {
         *reinterpret_cast<u32x4*>(P.C + (int64_t)gm * P.ldc + gn) = y;
         float v[8], o[8];
-        g_unpack8(y, v);
+        unpack8(y, v);
 #pragma unroll
         for (int k = 0; k < 8; k += 2) {
             const f32x2 r = g_gelu2(f32x2{v[k], v[k + 1]});
             o[k] = r[0]; o[k + 1] = r[1];
         }
-        *reinterpret_cast<u32x4*>(P.C2 + (int64_t)gm * P.ldc + gn) = g_pack8(o);
+        *reinterpret_cast<u32x4*>(P.C2 + (int64_t)gm * P.ldc + gn) = pack8(o);
     } else if (P.mode == 4) {
         float gq[8], v[8], d[8];
-        g_unpack8(y, gq);
-        g_unpack8(xa, v);
+        unpack8(y, gq);
+        unpack8(xa, v);
 #pragma unroll
         for (int k = 0; k < 8; k += 2) {
             const f32x2 r = f32x2{gq[k], gq[k + 1]} * g_gelu_grad2(f32x2{v[k], v[k + 1]});
             d[k] = r[0]; d[k + 1] = r[1];
         }
-        *reinterpret_cast<u32x4*>(P.C + (int64_t)gm * P.ldc + gn) = g_pack8(d);
+        *reinterpret_cast<u32x4*>(P.C + (int64_t)gm * P.ldc + gn) = pack8(d);
     } else if (P.mode == 5) {                      // ReLU': pass y where the saved activation is positive
         u32x4 o;
 #pragma unroll
@@ -299,13 +268,13 @@ __device__ __forceinline__ void g_epi_finish(const GemmP& P, int gm, int gn, con
         *reinterpret_cast<u32x4*>(P.C + (int64_t)gm * P.ldc + gn) = o;
     } else {                                       // mode 3
         float yv[8], xv[8];
-        g_unpack8(y, yv);
+        unpack8(y, yv);
         const int64_t o = tok * P.N + gn;
         if (P.res_dtype == DGX_BF16) {
-            g_unpack8(xa, xv);
+            unpack8(xa, xv);
 #pragma unroll
             for (int k = 0; k < 8; ++k) xv[k] += sc * yv[k];
-            *reinterpret_cast<u32x4*>((uint16_t*)P.out + o) = g_pack8(xv);
+            *reinterpret_cast<u32x4*>((uint16_t*)P.out + o) = pack8(xv);
         } else {
             f32x4 x0 = __builtin_bit_cast(f32x4, xa), x1 = __builtin_bit_cast(f32x4, xb);
 #pragma unroll

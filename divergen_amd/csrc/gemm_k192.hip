@@ -139,7 +139,7 @@ __global__ __launch_bounds__(KwCfg<AR>::WAVES * 64, 1) void gemm_k192_kernel(KwP
             bool ok = gm < P.M;
             if (P.mode == 3 && ok) {
                 int b = 0;
-                tok = g_row_token(P.map, gm, b);
+                tok = wm_row_token<int64_t, G_ORDERS>(P.map, (int64_t)gm, b);
                 ok = tok >= 0;
                 if (ok && P.scale) sc = P.scale[b];
             }

@@ -365,7 +365,7 @@ __global__ __launch_bounds__(256) void gemm_splitk_fold_kernel(GemmP P) {
         }
         if (P.bias) {
             float bv[8];
-            g_unpack8(*reinterpret_cast<const u32x4*>(P.bias + gn), bv);
+            unpack8(*reinterpret_cast<const u32x4*>(P.bias + gn), bv);
 #pragma unroll
             for (int k = 0; k < 8; ++k) v[k] += bv[k];
         }
@@ -373,11 +373,11 @@ __global__ __launch_bounds__(256) void gemm_splitk_fold_kernel(GemmP P) {
         float sc = 1.0f;
         if (P.mode == 3) {
             int b = 0;
-            tok = g_row_token(P.map, gm, b);
+            tok = wm_row_token<int64_t, G_ORDERS>(P.map, (int64_t)gm, b);
             if (tok < 0) continue;
             if (P.scale) sc = P.scale[b];
         }
-        g_epilogue_chunk(P, gm, gn, g_pack8(v), tok, sc);
+        g_epilogue_chunk(P, gm, gn, pack8(v), tok, sc);
     }
 }
 
@@ -517,16 +517,12 @@ extern "C" int dgx_gemm_bf16_nt(const void* A, const void* B, int M, int N, int 
             break;
         case DGX_EPI_BIAS_RESIDUAL: {
             // ws < 0: the rows are in COMPACT window order (winmap.h: real tokens only, M = B*H*W)
-            const int aws = ep->ws < 0 ? -ep->ws : ep->ws;
-            if (!ep->residual || !ep->out || ep->B <= 0 || ep->H <= 0 || ep->W <= 0 || ep->B > 4095 || ep->shift < 0 ||
-                (aws > 0 && ep->shift >= aws) || (ep->residual_dtype != DGX_F32 && ep->residual_dtype != DGX_BF16) ||
-                (ep->ws < 0 && !wm_compact_ok(ep->H, ep->W, aws, ep->shift)))
+            if (!ep->residual || !ep->out || ep->B <= 0 || ep->H <= 0 || ep->W <= 0 || ep->B > 4095 ||
+                (ep->residual_dtype != DGX_F32 && ep->residual_dtype != DGX_BF16) ||
+                !wm_map_ok(ep->B, ep->H, ep->W, ep->ws, ep->shift, G_ORDERS))
                 return DGX_ERR_BAD_ARG;
-            GMap m = {ep->B, ep->H, ep->W, aws, ep->shift, 0, 0, ep->ws < 0 ? 1 : 0};
-            if (aws > 0) { m.nWh = (ep->H + aws - 1) / aws; m.nWw = (ep->W + aws - 1) / aws; }
-            const int64_t rows = ep->ws > 0 ? (int64_t)ep->B * m.nWh * m.nWw * aws * aws : (int64_t)ep->B * ep->H * ep->W;
-            if (rows != M) return DGX_ERR_BAD_ARG;
-            P.map = m;
+            P.map = wm_map(ep->B, ep->H, ep->W, ep->ws, ep->shift);
+            if ((ep->ws > 0 ? wm_classic_rows(P.map) : (int64_t)ep->B * ep->H * ep->W) != M) return DGX_ERR_BAD_ARG;
             break;
         }
         default: return DGX_ERR_BAD_ARG;

@@ -9,16 +9,8 @@
 #include "dgx_common.h"
 
 namespace {
-__device__ __forceinline__ void unpack8(const u32x4 r, float (&v)[8]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { v[2 * i] = __uint_as_float(r[i] << 16); v[2 * i + 1] = __uint_as_float(r[i] & 0xffff0000u); }
-}
-__device__ __forceinline__ u32x4 pack8(const float (&v)[8]) {
-    return u32x4{pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7])};
-}
 __device__ __forceinline__ float block_sum(float v, float* red) {   // 256 threads
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    v = wave_sum(v);
     const int w = threadIdx.x >> 6;
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[w] = v;
@@ -264,7 +256,7 @@ __device__ __forceinline__ void gn_param_wave_store(float (&acc)[16], float* __r
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o);
+        for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o);      // (not wave_sum: the 16 sums then interleave otherwise and gn_bwd_param_* measured slower)
     }
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll

@@ -35,9 +35,7 @@ template <typename T> __device__ __forceinline__ float wave_row_softplus(const T
         for (int k = 0; k < N; ++k)
             if (c + k < C1) a += softplus(f[k]);      // a select, not a product: the pad columns may hold anything (NaN)
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
-    return a;
+    return wave_sum(a);
 }
 
 // block-wide (256 threads) integer sum / maximum; every thread returns the result

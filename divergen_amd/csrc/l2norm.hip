@@ -11,30 +11,6 @@
 #define L2N_EPS 1e-12f
 #define L2N_WAVES 4
 
-__device__ __forceinline__ float l2n_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// 8 consecutive elements of a row (chunk i) as fp32
-template <typename T> __device__ __forceinline__ void l2n_ld8(const T* row, int i, float (&v)[8]);
-template <> __device__ __forceinline__ void l2n_ld8<uint16_t>(const uint16_t* row, int i, float (&v)[8]) {
-    const uint4 d = reinterpret_cast<const uint4*>(row)[i];
-    v[0] = __uint_as_float(d.x << 16); v[1] = __uint_as_float(d.x & 0xffff0000u);
-    v[2] = __uint_as_float(d.y << 16); v[3] = __uint_as_float(d.y & 0xffff0000u);
-    v[4] = __uint_as_float(d.z << 16); v[5] = __uint_as_float(d.z & 0xffff0000u);
-    v[6] = __uint_as_float(d.w << 16); v[7] = __uint_as_float(d.w & 0xffff0000u);
-}
-template <> __device__ __forceinline__ void l2n_ld8<float>(const float* row, int i, float (&v)[8]) {
-    const float4 a = reinterpret_cast<const float4*>(row)[2 * i], b = reinterpret_cast<const float4*>(row)[2 * i + 1];
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-__device__ __forceinline__ void l2n_st8(uint16_t* row, int i, const float (&v)[8]) {
-    reinterpret_cast<uint4*>(row)[i] = make_uint4(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7]));
-}
-
 // NJ = ceil(D / 512) chunks of 8 elements per lane.  Lanes beyond the row's last chunk load that last chunk again (a clamped
 // index keeps the loads unpredicated and in flight together) and contribute zero.
 template <typename XT, int NJ>
@@ -48,7 +24,7 @@ __global__ __launch_bounds__(64 * L2N_WAVES) void l2n_fwd_kernel(const XT* __res
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             const int c = lane + 64 * j;
-            l2n_ld8<XT>(xr, c < nc ? c : nc - 1, v[j]);
+            ld8(xr + 8 * (c < nc ? c : nc - 1), v[j]);
         }
         float ss = 0.f;
 #pragma unroll
@@ -60,7 +36,7 @@ __global__ __launch_bounds__(64 * L2N_WAVES) void l2n_fwd_kernel(const XT* __res
             ss += ((v[j][0] * v[j][0] + v[j][1] * v[j][1]) + (v[j][2] * v[j][2] + v[j][3] * v[j][3])) +
                   ((v[j][4] * v[j][4] + v[j][5] * v[j][5]) + (v[j][6] * v[j][6] + v[j][7] * v[j][7]));
         }
-        const float rn = 1.0f / fmaxf(sqrtf(l2n_wave_sum(ss)), L2N_EPS);
+        const float rn = 1.0f / fmaxf(sqrtf(wave_sum(ss)), L2N_EPS);
         if (lane == 0) rnorm[row] = rn;
         const float s = t * rn;
         uint16_t* yr = y + row * D;
@@ -71,7 +47,7 @@ __global__ __launch_bounds__(64 * L2N_WAVES) void l2n_fwd_kernel(const XT* __res
                 float o[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) o[e] = v[j][e] * s;
-                l2n_st8(yr, c, o);
+                st8(yr + 8 * c, o);
             }
         }
     }
@@ -92,8 +68,8 @@ __global__ __launch_bounds__(64 * L2N_WAVES) void l2n_bwd_kernel(const uint16_t*
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             const int c = lane + 64 * j, ci = c < nc ? c : nc - 1;
-            l2n_ld8<XT>(xr, ci, v[j]);
-            l2n_ld8<uint16_t>(gr, ci, gv[j]);
+            ld8(xr + 8 * (ci), v[j]);
+            ld8(gr + 8 * (ci), gv[j]);
         }
         const float rn = rnorm[row];
         float dot = 0.f;
@@ -109,7 +85,7 @@ __global__ __launch_bounds__(64 * L2N_WAVES) void l2n_bwd_kernel(const uint16_t*
         const bool clamped = rn >= 1.0f / L2N_EPS;
         // xh . g = rn * dot;  dx = t*rn*(g - x*rn*(xh . g)) = s*g - x*(s*rn*rn*dot)
         const float s = t * rn;
-        const float k = clamped ? 0.f : s * rn * (rn * l2n_wave_sum(dot));
+        const float k = clamped ? 0.f : s * rn * (rn * wave_sum(dot));
         uint16_t* dr = dx + row * D;
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
@@ -118,7 +94,7 @@ __global__ __launch_bounds__(64 * L2N_WAVES) void l2n_bwd_kernel(const uint16_t*
                 float o[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) o[e] = s * gv[j][e] - v[j][e] * k;
-                l2n_st8(dr, c, o);
+                st8(dr + 8 * c, o);
             }
         }
     }

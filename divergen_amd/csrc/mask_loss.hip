@@ -37,9 +37,7 @@ __global__ __launch_bounds__(256) void mask_bce_partial_kernel(const T* __restri
     __shared__ float red[4][NV];
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
-        float v = acc[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        const float v = wave_sum(acc[k]);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
     }
     __syncthreads();

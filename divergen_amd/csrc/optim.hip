@@ -172,8 +172,7 @@ __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float4* __rest
         const float4 v = g[i];
         s += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);

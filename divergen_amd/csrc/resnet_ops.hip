@@ -8,17 +8,6 @@
 // All HBM-bound, 16 bytes per lane along the channel dimension.
 #include "dgx_common.h"
 
-namespace {
-__device__ __forceinline__ void rn_unpack8(const uint4 r, float (&v)[8]) {
-    const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { v[2 * i] = __uint_as_float(w[i] << 16); v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
-}
-__device__ __forceinline__ uint4 rn_pack8(const float (&v)[8]) {
-    return make_uint4(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7]));
-}
-}  // namespace
-
 // rows[(n, oy, ox)][c*49 + ky*7 + kx] = x[n][c][2 oy - 3 + ky][2 ox - 3 + kx] (0 outside), columns 147 .. 151 zero
 __global__ __launch_bounds__(256) void stem_im2col7x7_kernel(const float* __restrict__ x, uint4* __restrict__ rows, int N, int H, int W,
                                                              int Ho, int Wo) {
@@ -42,7 +31,7 @@ __global__ __launch_bounds__(256) void stem_im2col7x7_kernel(const float* __rest
             }
             v[k] = val;
         }
-        rows[i] = rn_pack8(v);
+        rows[i] = pack8<uint4>(v);
     }
 }
 
@@ -64,15 +53,15 @@ __global__ __launch_bounds__(256) void affine_act_fwd_kernel(const uint4* __rest
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int c0 = (int)(i % vecC) * 8;
         float v[8], r[8];
-        rn_unpack8(x[i], v);
-        if (res) rn_unpack8(res[i], r);
+        unpack8(x[i], v);
+        if (res) unpack8(res[i], r);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             float o = v[k] * scale[c0 + k] + shift[c0 + k];
             if (res) o += r[k];
             v[k] = (relu && !(o > 0.f)) ? 0.f : o;
         }
-        y[i] = rn_pack8(v);
+        y[i] = pack8<uint4>(v);
     }
 }
 // g = dy * [y > 0] (ReLU) ; dx = g * scale[c] ; dres = g (when asked for; may be the same buffer as dy)
@@ -82,16 +71,16 @@ __global__ __launch_bounds__(256) void affine_act_bwd_kernel(const uint4* __rest
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int c0 = (int)(i % vecC) * 8;
         float g[8], o[8], d[8];
-        rn_unpack8(dy[i], g);
+        unpack8(dy[i], g);
         if (relu) {
-            rn_unpack8(y[i], o);
+            unpack8(y[i], o);
 #pragma unroll
             for (int k = 0; k < 8; ++k) g[k] = o[k] > 0.f ? g[k] : 0.f;
         }
 #pragma unroll
         for (int k = 0; k < 8; ++k) d[k] = g[k] * scale[c0 + k];
-        dx[i] = rn_pack8(d);
-        if (dres) dres[i] = rn_pack8(g);
+        dx[i] = pack8<uint4>(d);
+        if (dres) dres[i] = pack8<uint4>(g);
     }
 }
 
@@ -139,13 +128,13 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_fwd_kernel(const uint4* __re
             const int iy = 2 * oy - 1 + tap / 3, ix = 2 * ox - 1 + tap % 3;
             if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
             float c[8];
-            rn_unpack8(x[(((int64_t)n * H + iy) * W + ix) * vecC + v], c);
+            unpack8(x[(((int64_t)n * H + iy) * W + ix) * vecC + v], c);
 #pragma unroll
             for (int k = 0; k < 8; ++k)
                 if (!any || c[k] > best[k] || c[k] != c[k]) { best[k] = c[k]; arg[k] = (uint32_t)tap; }
             any = true;
         }
-        y[i] = rn_pack8(best);
+        y[i] = pack8<uint4>(best);
         idx[i] = make_uint2(arg[0] | (arg[1] << 8) | (arg[2] << 16) | (arg[3] << 24), arg[4] | (arg[5] << 8) | (arg[6] << 16) | (arg[7] << 24));
     }
 }
@@ -169,14 +158,14 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_bwd_kernel(const uint4* __re
                 const int64_t o = (((int64_t)n * Ho + oy) * Wo + ox) * vecC + v;
                 const uint2 a = idx[o];
                 float g[8];
-                rn_unpack8(dy[o], g);
+                unpack8(dy[o], g);
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     const uint32_t w = k < 4 ? (a.x >> (8 * k)) & 0xffu : (a.y >> (8 * (k - 4))) & 0xffu;
                     if (w == tap) acc[k] += g[k];
                 }
             }
-        dx[i] = rn_pack8(acc);
+        dx[i] = pack8<uint4>(acc);
     }
 }
 

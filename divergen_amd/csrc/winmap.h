@@ -1,3 +1,7 @@
+// The window map of the Swin token-stream kernels (LayerNorm, residual, window gather / scatter, the GEMM residual epilogue, attention):
+// the classic window order, the compact one and the identity behind ONE struct (WmMap, at the end of this header), each direction
+// written once.  Host and device; tests/native/winmap_check.cpp checks all of it on the CPU against a brute-force table.
+//
 // Compact window order (round 6): the rows between a Swin block's LayerNorm-1 and its proj GEMM without the padding tokens.
 //
 // The reference zero-pads the (H, W) token grid to multiples of the window size BEFORE the cyclic shift and the partition
@@ -91,4 +95,84 @@ __host__ __device__ __forceinline__ int wm_token_of_row(const WmGeom& g, int row
     if (hh >= Hp) hh -= Hp;
     if (ww >= Wp) ww -= Wp;
     return (b * g.H + hh) * g.W + ww;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// The whole map.  ws == 0: identity (rows are tokens);  compact == 0: classic order, B*nWh*nWw*ws^2 rows, the padding tokens' rows
+// included;  compact == 1: compact order, rows 0 .. B*H*W-1 are the real tokens and whatever rows a buffer has beyond them are padding.
+struct WmMap { int B, H, W, ws, shift, nWh, nWw, compact; };
+
+// from the ABI's signed window size: ws < 0 means the compact order with window size -ws
+__host__ __device__ __forceinline__ WmMap wm_map(int B, int H, int W, int ws, int shift) {
+    WmMap m = {B, H, W, ws < 0 ? -ws : ws, shift, 0, 0, ws < 0 ? 1 : 0};
+    if (m.ws > 0) { m.nWh = (H + m.ws - 1) / m.ws; m.nWw = (W + m.ws - 1) / m.ws; }
+    return m;
+}
+// rows of a classic window-order buffer
+__host__ __device__ __forceinline__ int64_t wm_classic_rows(const WmMap& m) { return (int64_t)m.B * m.nWh * m.nWw * m.ws * m.ws; }
+
+// The orders a site implements: its entry point passes them to wm_map_ok, its kernel to the maps below, which then hold no code for the
+// others.  WM_COMPACT: every row of the buffer is a real token (B*H*W rows);  WM_COMPACT_TAIL: the buffer may keep rows behind them,
+// which are padding.
+enum { WM_IDENTITY = 1, WM_CLASSIC = 2, WM_COMPACT = 4, WM_COMPACT_TAIL = 4 | 8, WM_ALL = 15 };
+
+// May an entry point take (B, H, W, signed ws, shift)?  0 <= shift (< |ws| for a window order), the compact order only where its bands
+// do not wrap, and B*H*W equal to the caller's own token count where it has one (T >= 0).
+__host__ __device__ __forceinline__ bool wm_map_ok(int B, int H, int W, int ws, int shift, int orders, int64_t T = -1) {
+    if (shift < 0 || (T >= 0 && (int64_t)B * H * W != T)) return false;
+    if (ws == 0) return (orders & WM_IDENTITY) != 0;
+    const int a = ws < 0 ? -ws : ws;
+    if (shift >= a) return false;
+    return ws > 0 ? (orders & WM_CLASSIC) != 0 : (orders & WM_COMPACT) && wm_compact_ok(H, W, a, shift);
+}
+
+// Row of a window-order buffer -> token index of the (B, H*W) stream, or -1 for a padding token's row; b: the row's image.
+// I: the index type, int where every row and token count is known to be below 2^31, int64_t elsewhere -- a 64-bit division is a software
+// sequence of ~150 VALU instructions, a large share of a kernel that handles two to four rows per wave.
+template <typename I, int ORDERS = WM_ALL> __host__ __device__ __forceinline__ I wm_row_token(const WmMap& m, I orow, int& b) {
+    if ((ORDERS & WM_IDENTITY) && m.ws == 0) {
+        b = (int)(orow / ((I)m.H * m.W));
+        return orow;
+    }
+    if ((ORDERS & WM_COMPACT) && m.compact) {
+        if ((ORDERS & WM_COMPACT_TAIL & ~WM_COMPACT) && orow >= (I)m.B * m.H * m.W) { b = 0; return -1; }
+        return wm_token_of_row(wm_geom(m.H, m.W, m.ws, m.shift), (int)orow, b);
+    }
+    const int N = m.ws * m.ws;
+    const int n = (int)(orow % N);
+    I t = orow / N;
+    const int wc = (int)(t % m.nWw);
+    t /= m.nWw;
+    const int wr = (int)(t % m.nWh);
+    b = (int)(t / m.nWh);
+    // position in the shifted, padded frame -> position in the un-shifted padded frame: roll(-shift), shifted[h] = x[(h + shift) % Hp]
+    int hh = wr * m.ws + n / m.ws + m.shift, ww = wc * m.ws + n % m.ws + m.shift;
+    const int Hp = m.nWh * m.ws, Wp = m.nWw * m.ws;
+    if (hh >= Hp) hh -= Hp;
+    if (ww >= Wp) ww -= Wp;
+    if (hh >= m.H || ww >= m.W) return -1;
+    return ((I)b * m.H + hh) * m.W + ww;
+}
+template <typename I, int ORDERS = WM_ALL> __host__ __device__ __forceinline__ I wm_row_token(const WmMap& m, I orow) {
+    int b;
+    return wm_row_token<I, ORDERS>(m, orow, b);
+}
+
+// token (b, hh0, ww0) -> its row
+template <typename I, int ORDERS = WM_ALL> __host__ __device__ __forceinline__ I wm_token_row(const WmMap& m, int b, int hh0, int ww0) {
+    if ((ORDERS & WM_IDENTITY) && m.ws == 0) return ((I)b * m.H + hh0) * m.W + ww0;
+    if ((ORDERS & WM_COMPACT) && m.compact) return wm_row_of_token(wm_geom(m.H, m.W, m.ws, m.shift), b, hh0, ww0);
+    const int Hp = m.nWh * m.ws, Wp = m.nWw * m.ws;
+    int hs = hh0 - m.shift, wsx = ww0 - m.shift;
+    if (hs < 0) hs += Hp;
+    if (wsx < 0) wsx += Wp;
+    const int wr = hs / m.ws, wc = wsx / m.ws;
+    const int n = (hs - wr * m.ws) * m.ws + (wsx - wc * m.ws);
+    return (((I)b * m.nWh + wr) * m.nWw + wc) * (m.ws * m.ws) + n;
+}
+// token index -> its row (remainders by multiply-subtract from the quotients: one division per level in either width)
+template <typename I, int ORDERS = WM_ALL> __host__ __device__ __forceinline__ I wm_token_row(const WmMap& m, I tok) {
+    if ((ORDERS & WM_IDENTITY) && m.ws == 0) return tok;
+    const I t = tok / m.W, b = t / m.H;
+    return wm_token_row<I, ORDERS>(m, (int)b, (int)(t - b * m.H), (int)(tok - t * m.W));
 }

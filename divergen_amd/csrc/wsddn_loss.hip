@@ -133,8 +133,7 @@ __global__ __launch_bounds__(WS_THREADS) void wsddn_stats_kernel(const T* __rest
         }
     }
     if (tid < 64) {                                   // WS_CB = one wave: a fixed shuffle tree
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) neg += __shfl_xor(neg, o);
+        neg = wave_sum(neg);
         if (tid == 0) ws[(int64_t)P.B * 3 * C1 + (int64_t)i * ncb + blockIdx.x] = neg;
     }
     __syncthreads();

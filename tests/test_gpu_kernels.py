@@ -198,6 +198,50 @@ def test_layernorm_and_residual_epilogue_in_compact_window_order(B, H, W, C, ws,
     assert torch.equal(o_p, o_c)
 
 
+@pytest.mark.parametrize("B,H,W,ws,shift", [(2, 10, 13, 7, 3), (1, 14, 25, 12, 6), (2, 5, 9, 7, 3), (1, 12, 12, 12, 0)])
+def test_token_stream_kernels_share_one_classic_window_order(B, H, W, ws, shift):
+    """Window gather / scatter, the residual pair and the GEMM residual epilogue against ONE host table of the classic window order
+    (pad -> roll -> partition): a token-order tensor whose first 8 channels hold the base-256 digits of (token index + 1) -- exact in
+    bf16, and token 0 differs from the zero row of a padding token -- must arrive bit for bit in the table's rows, and come back.
+    H < ws and a grid without padding included; outputs are NaN beforehand."""
+    from divergen_amd import _lib as L
+    from divergen_amd.layers import gemm_ops as G
+    lib, st = L.lib(), L.stream()
+    T, C = B * H * W, 16
+    rows = _classic_rows(B, H, W, ws, shift)
+    Tw = rows.numel()
+    assert (Tw == T) == (H % ws == 0 and W % ws == 0)
+    x32 = torch.zeros(T, C)
+    x32[:, :8] = (((torch.arange(T) + 1)[:, None] >> (8 * torch.arange(8))[None]) & 255).float()
+    want = torch.where((rows >= 0)[:, None], x32[rows.clamp(min=0)], torch.zeros(1, C)).to(DEV)      # the host table applied
+    nan = lambda n, c, dt: torch.full((n, c), float("nan"), dtype=dt, device=DEV)  # noqa: E731
+    for dt in (torch.bfloat16, torch.float32):
+        x, code = x32.to(dt).to(DEV), L.DGX_BF16 if dt == torch.bfloat16 else L.DGX_F32
+        xw = nan(Tw, C, dt)
+        L.check(lib.dgx_window_gather(L.ptr(x), L.ptr(xw), B, H, W, C, ws, shift, code, st), "window_gather")
+        assert torch.equal(xw, want.to(dt))
+        back = nan(T, C, dt)
+        L.check(lib.dgx_window_scatter(L.ptr(xw), L.ptr(back), B, H, W, C, ws, shift, code, st), "window_scatter")
+        assert torch.equal(back, x)
+        dy = nan(Tw, C, torch.bfloat16)
+        L.check(lib.dgx_residual_bwd(L.ptr(x), None, L.ptr(dy), B, H, W, C, ws, shift, code, st), "residual_bwd")
+        assert torch.equal(dy, want.to(torch.bfloat16))
+        out = nan(T, C, dt)
+        zero = torch.zeros_like(x)
+        L.check(lib.dgx_residual_fwd(L.ptr(zero), L.ptr(dy), None, L.ptr(out), B, H, W, C, ws, shift, code, st), "residual_fwd")
+        assert torch.equal(out, x)
+        # residual epilogue of the GEMM at the smallest K = N = 8 it takes: identity weight, no bias, residual 0
+        a, eye = want[:, :8].to(torch.bfloat16).contiguous(), torch.eye(8, dtype=torch.bfloat16, device=DEV)
+        res, o, nobias = torch.zeros(T, 8, dtype=dt, device=DEV), nan(T, 8, dt), torch.zeros(8, dtype=torch.bfloat16, device=DEV)
+        ep = L.GemmEpilogue()
+        ep.mode = G.EPI_BIAS_RESIDUAL
+        ep.bias, ep.residual, ep.out, ep.scale = nobias.data_ptr(), res.data_ptr(), o.data_ptr(), None
+        ep.residual_dtype = code
+        ep.B, ep.H, ep.W, ep.ws, ep.shift = B, H, W, ws, shift
+        G._launch(a, eye, ep)
+        assert torch.equal(o, x[:, :8])
+
+
 @pytest.mark.parametrize("ws", [7, 12])
 def test_window_attention_vs_reference_golden(golden, ws):
     """Golden from the reference's own WindowAttention (fp32); kernel consumes its qkv in bf16."""
