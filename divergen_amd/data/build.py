@@ -26,7 +26,7 @@ import os
 import numpy as np
 import torch
 
-from ..structures import BitMasks, Boxes, Instances
+from ..structures import BitMasks, Boxes, Instances, PolygonCrossings
 from ..utils import comm
 from .samplers import RepeatFactorTrainingSampler, TrainingSampler
 
@@ -372,6 +372,17 @@ def polygons_to_bitmask(polygons, h, w, out=None):
     return m
 
 
+def polygons_to_crossings(polygons, h, w):
+    """The polygons of one instance as dgx_polygons_to_bitmask takes them (INPUT.DEVICE_RASTER): per polygon the crossings of
+    polygon_crossings, those at or past h * w removed (a crossing clipped to the bottom of the last column), sorted ascending, int32.
+    What polygons_to_bitmask does after this point -- toggle counts, the XOR scan, the transposed write -- is the kernel's."""
+    out = []
+    for poly in polygons:
+        pos = polygon_crossings([float(c) for c in poly], h, w)
+        out.append(np.sort(pos[pos < h * w]).astype(np.int32))
+    return out
+
+
 # ----------------------------------------------------------------------------------------------- mapper
 def read_image(file_name, fmt="BGR"):
     """D2/data/detection_utils.py:read_image: PIL decode, EXIF orientation applied, RGB -> requested channel order."""
@@ -403,14 +414,17 @@ def transform_instance_annotations(anno, transforms, image_size):
     return anno
 
 
-def annotations_to_instances(annos, image_size):
-    """D2 annotations_to_instances with mask_format 'bitmask'."""
+def annotations_to_instances(annos, image_size, device_raster=False):
+    """D2 annotations_to_instances with mask_format 'bitmask'.  device_raster (INPUT.DEVICE_RASTER): no (N, h, w) block is allocated
+    or filled; gt_masks is a PolygonCrossings, the sorted crossing lists the training process fills on the device."""
     h, w = image_size
     target = Instances(image_size)
     boxes = np.stack([a["bbox"] for a in annos]) if annos else np.zeros((0, 4))
     target.gt_boxes = Boxes(torch.as_tensor(boxes, dtype=torch.float32).reshape(-1, 4))
     target.gt_classes = torch.tensor([int(a["category_id"]) for a in annos], dtype=torch.int64)
-    if annos and "segmentation" in annos[0]:
+    if annos and "segmentation" in annos[0] and device_raster:
+        target.gt_masks = PolygonCrossings.from_lists([polygons_to_crossings(a["segmentation"], h, w) for a in annos], image_size)
+    elif annos and "segmentation" in annos[0]:
         masks = np.zeros((len(annos), h, w), dtype=bool)          # one contiguous block: it is pinned and uploaded as it is
         for i, a in enumerate(annos):
             polygons_to_bitmask(a["segmentation"], h, w, out=masks[i])
@@ -422,7 +436,9 @@ def filter_empty_instances(instances, box_threshold=1e-5):
     """D2 filter_empty_instances(by_box=True, by_mask=True)."""
     b = instances.gt_boxes.tensor
     keep = ((b[:, 2] - b[:, 0]) > box_threshold) & ((b[:, 3] - b[:, 1]) > box_threshold)
-    if instances.has("gt_masks"):
+    if instances.has("gt_masks") and isinstance(instances.gt_masks, PolygonCrossings):
+        keep &= instances.gt_masks.nonempty()          # emptiness from the crossings: equal to the filled mask's .any()
+    elif instances.has("gt_masks"):
         gm = instances.gt_masks.tensor
         keep &= torch.from_numpy(gm.numpy().reshape(gm.shape[0], -1).any(1)) if not gm.is_cuda else gm.flatten(1).any(1)
     return instances[keep]
@@ -451,6 +467,8 @@ class DatasetMapper:
                                  for scale, size in zip(cfg.DATALOADER.DATASET_INPUT_SCALE, cfg.DATALOADER.DATASET_INPUT_SIZE)]
         self.image_format = cfg.INPUT.FORMAT
         self.use_instance_mask = cfg.MODEL.MASK_ON
+        # INPUT.DEVICE_RASTER: the training samples carry their polygons' crossing lists instead of dense masks
+        self.device_raster = bool(cfg.INPUT.get("DEVICE_RASTER", False)) and is_train
         if cfg.INPUT.MASK_FORMAT != "bitmask" and cfg.MODEL.MASK_ON and is_train:
             logger.warning("INPUT.MASK_FORMAT '%s': masks are rasterised to bitmasks on the loader side either way", cfg.INPUT.MASK_FORMAT)
 
@@ -480,7 +498,7 @@ class DatasetMapper:
                 if not self.use_instance_mask:
                     obj.pop("segmentation", None)
                 annos.append(transform_instance_annotations(obj, transforms, image_shape))
-            inst = filter_empty_instances(annotations_to_instances(annos, image_shape))
+            inst = filter_empty_instances(annotations_to_instances(annos, image_shape, self.device_raster))
             if not inst.has("gt_masks"):
                 inst.gt_masks = BitMasks(torch.zeros(0, image_shape[0], image_shape[1], dtype=torch.bool))
             d["instances"] = inst
@@ -517,6 +535,9 @@ class CopyPasteMapper:
         self.ring = None               # SlotRing the workers wrote the blobs into (build_detection_train_loader)
         self.self_prob = self._parse_method(self.method)      # None: no self copy; 1.0: always; f: 'p:<f>', per sample
         self.self_only = self.method == "self_copy"
+        self.device_raster = bool(cfg.INPUT.get("DEVICE_RASTER", False))
+        if self.device_raster:
+            self._check_device_raster(cfg)
         if self.self_prob is not None:
             self._check_self_copy(cfg)
         if self.src_modes:
@@ -586,6 +607,19 @@ class CopyPasteMapper:
         if bool(inp.get("ACTIVE_SELECT", False)):
             raise NotImplementedError("INPUT.ACTIVE_SELECT with INPUT.USE_COPY_METHOD '{}': BSGAL's origin / held-out samples are built "
                                       "for 'syn_copy' only".format(inp.USE_COPY_METHOD))
+
+    @staticmethod
+    def _check_device_raster(cfg):
+        """This build's key INPUT.DEVICE_RASTER is built for USE_COPY_METHOD 'none' and 'syn_copy' (with or without RM_BG_PROB under
+        INPUT.SCP_SRC_MODES, WITH_IMAGE_LABELS): there the masks are first read on the device.  The self-copy methods read the source's
+        masks in the WORKER (_call_self_copy selects and crops them), and BSGAL's held-out sample is indexed by class there."""
+        inp = cfg.INPUT
+        if CopyPasteMapper._parse_method(inp.USE_COPY_METHOD) is not None:
+            raise NotImplementedError("INPUT.DEVICE_RASTER with INPUT.USE_COPY_METHOD '{}': the self-copy methods read the source image's "
+                                      "masks in the loader worker; 'none' and 'syn_copy' are built".format(inp.USE_COPY_METHOD))
+        if bool(inp.get("ACTIVE_SELECT", False)):
+            raise NotImplementedError("INPUT.DEVICE_RASTER with INPUT.ACTIVE_SELECT: BSGAL's origin / held-out samples are built on dense "
+                                      "host masks")
 
     @staticmethod
     def _pastes_all(inp):
@@ -826,13 +860,14 @@ class CopyPasteMapper:
         """What the TRAINING PROCESS runs on one worker result, on the current stream: upload (asynchronous from pinned memory) and
         the compositor kernel; with INPUT.ACTIVE_SELECT the un-pasted sample stays available as origin_* (it is the uploaded
         input: the compositor writes a copy)."""
-        from .copypaste import InstPool
+        from .copypaste import InstPool, fill_device_masks
         dev = torch.device(device)
         own = "blob" in result                       # the sample's tensors come out of a device copy made here
         result = unpack_sample(result, dev, self.ring)
         if "instances" not in result:
             result["image"] = result["image"].to(dev, non_blocking=True)
             return result
+        result = fill_device_masks(result, dev)      # INPUT.DEVICE_RASTER: from here on the sample is what the key-off path carries
         if result.get("rm_bg"):
             result = self._finish_rm_bg(result, dev, own)
         if "paste_pack" in result and dev.type == "cuda":
@@ -876,10 +911,15 @@ def pack_sample(d):
     entries themselves are dropped.  Samples without paste_pack / instances pass through unchanged.  Sections: the four of the
     sample, the three of paste_pack when it has one, the four of the self-copy source (scp_src) when it has one -- four per group
     when scp_src is a list of source groups, counted by blob_scp_n; a sample without scp_src, and one with a single source, pack
-    exactly as they always did."""
+    exactly as they always did.  INPUT.DEVICE_RASTER: the instances' gt_masks is a PolygonCrossings, and the sections poly_pos (int32),
+    poly_off and inst_off (int64) stand where gt_masks would."""
     if ("paste_pack" not in d and "scp_src" not in d) or "instances" not in d or not d["instances"].has("gt_masks"):
         return d
     fields = _BLOB_FIELDS if "paste_pack" in d else _BLOB_FIELDS[:4]
+    gm = d["instances"].gt_masks
+    if isinstance(gm, PolygonCrossings):      # INPUT.DEVICE_RASTER: three small sections in place of gt_masks
+        fields = fields[:1] + tuple((name, lambda d, a=a: torch.from_numpy(a)) for name, a in
+                                    (("poly_pos", gm.pos), ("poly_off", gm.poly_off), ("inst_off", gm.inst_off))) + fields[2:]
     multi = isinstance(d.get("scp_src"), list)
     groups = []
     if multi:
@@ -934,10 +974,12 @@ def unpack_sample(d, device, ring=None):
     if d.get("blob_slot") is not None:
         from .. import _lib as L
         off, n = d["blob_slot"]
+        host = ring.buf[off:off + n]
         blob = torch.empty(n, dtype=torch.uint8, device=device)
         L.check(L.lib().dgx_memcpy_h2d_async(blob.data_ptr(), ring.buf.data_ptr() + off, n, L.stream()), "dgx_memcpy_h2d_async")
     else:
-        blob = d["blob"].to(device, non_blocking=True)
+        host = d["blob"]
+        blob = host.to(device, non_blocking=True)
     f = {}
     for name, dt, shape, off in d["blob_layout"]:
         dtype = getattr(torch, dt)
@@ -945,7 +987,20 @@ def unpack_sample(d, device, ring=None):
         f[name] = blob[off:off + n].view(dtype).view(shape)
     out = {k: v for k, v in d.items() if not k.startswith("blob")}
     out["image"] = f["image"]
-    inst = Instances(tuple(d["blob_hw"]), gt_boxes=Boxes(f["gt_boxes"]), gt_classes=f["gt_classes"], gt_masks=BitMasks(f["gt_masks"].view(torch.bool)))
+    if "poly_pos" in f:
+        # INPUT.DEVICE_RASTER: the offsets are validated on the host before a kernel indexes with them -- read from the host side of the
+        # blob (a copy: the slot is rewritten later), while the kernel reads the sections of the device copy
+        sec = {name: (dt, shape, off) for name, dt, shape, off in d["blob_layout"]}
+
+        def on_host(name):
+            dt, shape, off = sec[name]
+            a = np.dtype(dt)
+            return host[off:off + int(np.prod(shape)) * a.itemsize].numpy().view(a).copy()
+        masks = PolygonCrossings(on_host("poly_pos"), on_host("poly_off"), on_host("inst_off"), tuple(d["blob_hw"]),
+                                 device_copy=(f["poly_pos"], f["poly_off"], f["inst_off"]))
+    else:
+        masks = BitMasks(f["gt_masks"].view(torch.bool))
+    inst = Instances(tuple(d["blob_hw"]), gt_boxes=Boxes(f["gt_boxes"]), gt_classes=f["gt_classes"], gt_masks=masks)
     for k, v in d.get("blob_extra_fields", {}).items():
         inst.set(k, v.to(device) if hasattr(v, "to") else v)
     out["instances"] = inst
@@ -1127,6 +1182,19 @@ class BatchAhead:
 # throttled the whole cgroup, and the training thread's host time per step DOUBLED (profiles/r06_loader_ab.txt: 57.0 ms/step with the
 # default pool, 28.5 with 4 threads, same workers, same batches; 25.2 with the same batches and no loader running).  The training
 # process has no CPU tensor work of its own besides those copies.  bench.py --loader-dev main_threads=N overrides (0 = leave alone).
+DEVICE_RASTER_CROSSING_BYTES = 4 << 20      # ring-slot allowance for one sample's crossing lists with INPUT.DEVICE_RASTER
+
+
+def ring_slot_bytes(size, self_copy_sources=0, device_raster=False):
+    """Bytes of one SlotRing slot at TRAIN_SIZE `size`: 48 planes (the image and ~45 dense masks), 48 more per self-copy source, and
+    8 MB for the rest of the blob.  INPUT.DEVICE_RASTER: no mask planes travel -- the 3 image planes, the same 8 MB, and
+    DEVICE_RASTER_CROSSING_BYTES for the crossing lists and their offsets (4 bytes per crossing: room for a million, where 12 polygons
+    of 120 vertices across 800 px make 70 000) -- never more than the slot without the key, which a small TRAIN_SIZE would otherwise
+    fall below; a sample beyond its slot takes the ordinary way, as any blob larger than its slot does."""
+    dense = size * size * (48 + 48 * int(self_copy_sources)) + (8 << 20)
+    if device_raster:
+        return min(dense, size * size * 3 + (8 << 20) + DEVICE_RASTER_CROSSING_BYTES)
+    return dense
 DEV = {"pin": "ring", "strategy": None, "main_threads": 4}      # pin: "ring" (SlotRing) | "loader" (the DataLoader's pin thread) | "none"
 
 
@@ -1160,6 +1228,9 @@ def build_detection_train_loader(cfg, per_gpu, device, seed):
     else:
         raise ValueError("Unknown training sampler: {}".format(name))
     mapper = CopyPasteMapper(DatasetMapper(cfg, True), cfg)
+    if mapper.device_raster and torch.device(device).type != "cuda":
+        raise NotImplementedError("INPUT.DEVICE_RASTER with device '{}': the masks are filled by dgx_polygons_to_bitmask on the GPU; "
+                                  "there is no host fill behind the key".format(device))
     mapper.set_dataset(dicts)
     rank_seed = seed * 1009 + comm.get_rank() * 131
     nw = cfg.DATALOADER.NUM_WORKERS
@@ -1173,11 +1244,10 @@ def build_detection_train_loader(cfg, per_gpu, device, seed):
         # one slot holds an image with up to ~45 ground-truth masks at TRAIN_SIZE^2 (more: that sample takes the ordinary way)
         # with a self-copy method the sample also carries the source image (3 planes) and up to 99 selected source masks, each at most
         # TRAIN_SIZE^2: room for ~45 more planes (the mean of the draw over a 90-object image); beyond that, the ordinary way again
-        size = int(cfg.INPUT.TRAIN_SIZE)
         # (INPUT.SCP_NUM_SRC sources: that many times the source's share)
-        planes = 48 if mapper.self_prob is None else 48 + 48 * int(mapper.num_src)
+        slot = ring_slot_bytes(int(cfg.INPUT.TRAIN_SIZE), 0 if mapper.self_prob is None else int(mapper.num_src), mapper.device_raster)
         try:
-            ring = SlotRing(nw, (int(cfg.DATALOADER.PREFETCH_FACTOR) + 2) * per_gpu, size * size * planes + (8 << 20))
+            ring = SlotRing(nw, (int(cfg.DATALOADER.PREFETCH_FACTOR) + 2) * per_gpu, slot)
         except Exception as e:
             logger.warning("loader: no page-locked slot ring (%s); falling back to the DataLoader's pin thread", e)
             pin_thread = True

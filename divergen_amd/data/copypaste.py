@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from ..layers.copy_paste import BLEND_MODES, BLEND_MODES_ALL, PackedPastes, copy_paste
-from ..structures import BitMasks, Boxes, Instances
+from ..structures import BitMasks, Boxes, Instances, PolygonCrossings
 
 
 def check_cp_method(cp_method, allow_poisson=False):
@@ -57,6 +57,21 @@ def result_instances(out, with_source=True):
     if with_source:
         inst.instance_source = out["source"]
     return inst
+
+
+def fill_device_masks(data, device):
+    """INPUT.DEVICE_RASTER, training-process half: a sample whose instances carry PolygonCrossings gets its BitMasks here -- ONE
+    dgx_polygons_to_bitmask launch into a fresh device tensor on the CURRENT stream (the loader's side stream), in front of
+    dgx_remove_background and the compositor.  Any other sample is returned as it is."""
+    inst = data.get("instances")
+    if inst is None or not inst.has("gt_masks") or not isinstance(inst.gt_masks, PolygonCrossings):
+        return data
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("INPUT.DEVICE_RASTER needs the GPU kernel (dgx_polygons_to_bitmask); device is %s" % device)
+    filled = Instances(inst.image_size)
+    for name, value in inst.get_fields().items():
+        filled.set(name, value.rasterize(device) if name == "gt_masks" else value)
+    return dict(data, instances=filled)
 
 
 def largest_connected_component(mask):
@@ -254,6 +269,7 @@ class InstPool:
         """Training-process half: the prepared sample's tensors go to `device` (asynchronously when they are pinned) and ONE
         libdgx call (copy_paste) on the CURRENT stream blends all K patches, updates masks / boxes and drops covered objects.  The
         caller chooses the stream (data/build.py: a side stream, one batch ahead of the training stream)."""
+        data = fill_device_masks(data, device)       # INPUT.DEVICE_RASTER: the ground-truth masks are filled here, before they are read
         pk = data["paste_pack"]
         inst = data["instances"]
         H, W = data["image"].shape[-2:]

@@ -1,8 +1,9 @@
-"""Batched-input contract types: Boxes, Instances, ImageList, BitMasks.
+"""Batched-input contract types: Boxes, Instances, ImageList, BitMasks (and PolygonCrossings, what BitMasks is filled from).
 Surface of D2/structures/{boxes.py:130-357, instances.py, image_list.py:59-110, masks.py:88-245}."""
 import itertools
 from typing import Any, Dict, List, Tuple
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -157,6 +158,75 @@ class BitMasks:
     @staticmethod
     def cat(lst):
         return BitMasks(torch.cat([m.tensor for m in lst], dim=0))
+
+
+def crossings_nonempty(pos):
+    """Whether the mask of ONE polygon has a pixel, from its crossing list alone (ascending flat positions, those past the canvas
+    removed): the fill is set on [pos[0], pos[1]), [pos[2], pos[3]), ... and, for an odd list, from its last crossing to the end of the
+    canvas -- so it is non-empty iff some even index k has pos[k + 1] > pos[k], or the count is odd."""
+    pos = np.asarray(pos)
+    n = pos.size
+    return bool(n & 1) or bool((pos[1:n:2] > pos[0:n - 1:2]).any())
+
+
+class PolygonCrossings:
+    """What BitMasks would have carried for the N instances of one image, before the fill (INPUT.DEVICE_RASTER): per polygon the sorted
+    column-major crossing positions of data/build.py:polygon_crossings, those past the canvas removed.
+      pos int32 (n_pos), poly_off int64 (P + 1) into pos, inst_off int64 (N + 1) into the polygons -- numpy arrays on the host.
+    A loader worker builds, filters (nonempty) and indexes it; the training process turns it into BitMasks on the device with ONE
+    dgx_polygons_to_bitmask launch (rasterize).  `device_copy`: (pos, poly_off, inst_off) already on the device (views of the
+    uploaded sample blob), used by rasterize instead of an upload of its own; indexing drops it."""
+
+    def __init__(self, pos, poly_off, inst_off, image_size, device_copy=None):
+        self.pos = np.ascontiguousarray(pos, dtype=np.int32).reshape(-1)
+        self.poly_off = np.ascontiguousarray(poly_off, dtype=np.int64).reshape(-1)
+        self.inst_off = np.ascontiguousarray(inst_off, dtype=np.int64).reshape(-1)
+        self.image_size = tuple(int(v) for v in image_size)
+        self.device_copy = device_copy
+        if self.inst_off.size < 1 or self.poly_off.size < 1 or self.inst_off[-1] != self.poly_off.size - 1 or self.poly_off[-1] != self.pos.size:
+            raise ValueError("PolygonCrossings: offsets end at %s / %s for %d polygons / %d crossings" % (
+                self.inst_off[-1:].tolist(), self.poly_off[-1:].tolist(), self.poly_off.size - 1, self.pos.size))
+
+    @classmethod
+    def from_lists(cls, per_instance, image_size):
+        """per_instance: for every instance the list of its polygons' sorted, canvas-filtered crossing arrays."""
+        polys = [np.asarray(p, dtype=np.int32) for inst in per_instance for p in inst]
+        poly_off = np.zeros(len(polys) + 1, dtype=np.int64)
+        inst_off = np.zeros(len(per_instance) + 1, dtype=np.int64)
+        if polys:
+            np.cumsum([p.size for p in polys], out=poly_off[1:])
+        if per_instance:
+            np.cumsum([len(inst) for inst in per_instance], out=inst_off[1:])
+        pos = np.concatenate(polys) if polys else np.zeros(0, dtype=np.int32)
+        return cls(pos, poly_off, inst_off, image_size)
+
+    def __len__(self):
+        return self.inst_off.size - 1
+
+    def polygons(self, i):
+        """The crossing arrays of instance i's polygons."""
+        return [self.pos[self.poly_off[p]:self.poly_off[p + 1]] for p in range(self.inst_off[i], self.inst_off[i + 1])]
+
+    def nonempty(self):
+        """(N,) bool tensor: polygons_to_bitmask(instance).any() without the fill -- an instance has a pixel iff one of its polygons has."""
+        return torch.tensor([any(crossings_nonempty(p) for p in self.polygons(i)) for i in range(len(self))], dtype=torch.bool)
+
+    def __getitem__(self, item):
+        if isinstance(item, int):
+            item = slice(item, item + 1) if item >= 0 else slice(len(self) + item, len(self) + item + 1)
+        if isinstance(item, torch.Tensor):
+            item = item.cpu().numpy()
+        return PolygonCrossings.from_lists([self.polygons(i) for i in np.arange(len(self))[item]], self.image_size)
+
+    def rasterize(self, device):
+        """-> BitMasks (N, H, W) on `device`, filled by dgx_polygons_to_bitmask on the current stream."""
+        from ..layers.raster_ops import polygons_to_bitmask
+        H, W = self.image_size
+        dev = self.device_copy
+        if dev is None:
+            dev = tuple(torch.from_numpy(a).to(device, non_blocking=True) for a in (self.pos, self.poly_off, self.inst_off))
+        out = polygons_to_bitmask(dev[0], self.poly_off, self.inst_off, H, W, poly_off_dev=dev[1], inst_off_dev=dev[2])
+        return BitMasks(out.view(torch.bool))
 
 
 def _join_field(values):

@@ -463,6 +463,24 @@ int dgx_self_copy_paste_all(const uint8_t* dst_image, const uint8_t* dst_masks, 
  * nothing launched in either case. */
 int dgx_remove_background(const uint8_t* image, const uint8_t* masks, int n, int h, int w, uint8_t* out_image, void* stream);
 
+/* Ground-truth polygon fill (INPUT.DEVICE_RASTER): the byte masks of the N instances of one sample from the crossing lists of their
+ * polygons, byte for byte divergen_amd/data/build.py:polygons_to_bitmask per instance (pycocotools rleFrPoly + rleMerge, decoded).
+ *   pos i32 (n_pos), device: per polygon the column-major flat positions x * H + y that build.py:polygon_crossings returns, those
+ *       >= H * W removed, each polygon's list sorted ascending (the host sorts).  Positions are only compared, never dereferenced.
+ *   poly_off i64 (P + 1): polygon p owns pos[poly_off[p] .. poly_off[p + 1]);  inst_off i64 (N + 1): instance i owns the polygons
+ *       inst_off[i] .. inst_off[i + 1] - 1.  Both are given twice: the DEVICE copies the kernel reads and the HOST copies
+ *       (host_poly_off, host_inst_off, the same values) that are validated here before anything is launched -- start at 0, never
+ *       decrease, inst_off ends at P, poly_off ends at n_pos.
+ *   masks u8 (N, H, W) row-major, 0 / 1: pixel (y, x) of one polygon is 1 iff an odd number of its crossings lie at flat positions
+ *       <= x * H + y (parity runs in flat order, across column boundaries; an odd list leaves the rest of the canvas set); an instance
+ *       is the OR of its polygons; an instance without polygons is a zero plane.  EVERY byte is written: masks need not be cleared.
+ * One launch, no floating point, no atomics: two calls give the same bytes.  Must move N * H * W bytes out and 4 * n_pos in.
+ * N == 0 -> DGX_OK, nothing launched.  Errors, nothing launched: N, P or n_pos < 0, H or W <= 0, a NULL array that would be used, or
+ * offsets that fail the validation -> DGX_ERR_BAD_ARG;  H * W >= 2^31 or n_pos >= 2^31 -> DGX_ERR_UNSUPPORTED. */
+int dgx_polygons_to_bitmask(const int32_t* pos, int64_t n_pos, const int64_t* poly_off, const int64_t* inst_off,
+                            const int64_t* host_poly_off, const int64_t* host_inst_off, int N, int P, int H, int W,
+                            uint8_t* masks, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Fused parameter update over a flat arena: per-element gradient value clip, AdamW, EMA lerp of
  * the PRE-step weights (the reference updates the EMA before optimizer.step: DG/train_net.py:262-284),
