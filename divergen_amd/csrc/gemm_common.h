@@ -1,17 +1,16 @@
 // Shared pieces of libdgx's forward / input-gradient GEMM kernels (gemm_nt.hip: 8 waves that load their own operands, two workgroups
 // per CU for the short contractions; gemm_lw.hip: 8 MFMA waves + 4 loader waves, persistent; gemm_k192.hip: resident weight panel):
-// problem descriptor, LDS-direct load helper, the operand addressing and split-K pieces the tiled kernels share, exact-GELU arithmetic
+// problem descriptor, the operand addressing and split-K pieces the tiled kernels share, exact-GELU arithmetic
 // and the fused tails of the read-out (bias | bias + GELU with both tensors | x GELU'(f1) |
 // x ReLU'(act) | window-reverse + DropPath + residual).
 #pragma once
-#include "dgx_common.h"
+#include "lds_direct.h"
 #include "gemm_plan.h"
 #include "winmap.h"
 #include <type_traits>
 
 constexpr int G_ORDERS = WM_IDENTITY | WM_CLASSIC | WM_COMPACT;      // the row orders of the residual epilogue (M rows, all of them tokens or classic rows)
 constexpr int GBK = 64;                 // K-step (elements): 128-byte tile rows
-static constexpr uint32_t G_OOB = 0x80000000u; // voffset beyond num_records: the lane's 16 bytes land in LDS as zeros
 
 namespace dgxgemm {
 struct GemmP {
@@ -53,21 +52,6 @@ using dgxgemm::GemmP;
 
 namespace {
 
-__device__ __forceinline__ void g_load_lds16(uint32_t voff, u32x4 rsrc, uint32_t lds_addr, uint32_t soff) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds" ::"v"(voff), "s"(rsrc), "s"(lds_addr), "s"(soff)
-                 : "memory");
-}
-__device__ __forceinline__ u32x4 g_rsrc(const void* base, uint32_t bytes) {
-    const uint64_t a = (uint64_t)base;
-    return u32x4{(uint32_t)a, (uint32_t)(a >> 32) & 0xffffu, bytes, 0x00020000u};
-}
-template <int N> __device__ __forceinline__ void g_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void g_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void g_bar() {
-    asm volatile("s_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-
 // The tail compiled into an instantiation: MC >= 0 fixes the mode (3 / 6: mode 3 with a bf16 / fp32 residual stream), MC < 0 leaves it
 // a run-time field.  With the mode a run-time field the tail's operand prefetch sat under mode branches, and the compiler's wait-count
 // model, merging the path without a prefetch, waited for every outstanding load (vmcnt(0)) before the staging pass the prefetch was
@@ -107,7 +91,7 @@ __device__ __forceinline__ void g_enter_group(GemmP& P, const dgxgemm::GemmP::Gr
     P.A = q.A; P.C = q.C; P.M = q.M;
     P.cmap_n = q.cn; P.cmap_h = q.ch; P.cmap_w = q.cw; P.conv_wp = q.wp;
 }
-// Byte offset of this lane's 16-byte chunk (logical chunk lc) of GEMM row m of the A operand, G_OOB for a row beyond M.  Implicit
+// Byte offset of this lane's 16-byte chunk (logical chunk lc) of GEMM row m of the A operand, BUF_OOB for a row beyond M.  Implicit
 // convolution: row m is output pixel (n, y, x), which reads its position in the zero-bordered image.
 __device__ __forceinline__ uint32_t g_a_voff(const GemmP& P, int m, int lc) {
     int64_t arow = m;
@@ -117,7 +101,7 @@ __device__ __forceinline__ uint32_t g_a_voff(const GemmP& P, int m, int lc) {
         const int y = r / P.cmap_w, x = r - y * P.cmap_w;
         arow = ((int64_t)n * (P.cmap_h + 2) + y + 1) * P.conv_wp + x + 1;
     }
-    return m < P.M ? (uint32_t)((arow * P.lda + lc * 8) * 2) : G_OOB;
+    return m < P.M ? (uint32_t)((arow * P.lda + lc * 8) * 2) : BUF_OOB;
 }
 // soffset of K-tile kta of the A operand; implicit convolution: tap shift (rows) + channel block of the tap
 __device__ __forceinline__ uint32_t g_a_soff(const GemmP& P, int kta) {

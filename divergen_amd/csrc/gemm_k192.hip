@@ -47,17 +47,17 @@ __global__ __launch_bounds__(KwCfg<AR>::WAVES * 64, 1) void gemm_k192_kernel(KwP
     const uint32_t lds0 = (uint32_t)(uintptr_t)(DGX_LDS unsigned char*)lds_raw;
     // ---- the panel: 3 K-tiles x 24 groups of 8 rows, one LDS-direct load instruction each, dealt over the six waves
     {
-        const u32x4 rB = g_rsrc(P.B, (uint32_t)((int64_t)P.N * P.ldb * 2));
+        const u32x4 rB = buf_rsrc(P.B, (uint32_t)((int64_t)P.N * P.ldb * 2));
         for (int idx = w; idx < KW_KT * 24; idx += KW_WAVES) {
             const int kt = idx / 24, q = idx - kt * 24;
             const int lc = (l & 7) ^ (((q & 1) << 2) | (rsub >> 1));
             const int n = n0 + 8 * q + rsub;
             const uint32_t voff = (uint32_t)(((int64_t)n * P.ldb + lc * 8) * 2);
-            g_load_lds16(voff, rB, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(kt * KW_BKT + q * 1024)), (uint32_t)kt * 128u);
+            lds_load16(voff, rB, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(kt * KW_BKT + q * 1024)), (uint32_t)kt * 128u);
         }
     }
     const uint32_t abase = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(KW_B_BYTES + w * KW_A_BYTES));
-    const u32x4 rA = g_rsrc(P.A, (uint32_t)((int64_t)P.M * P.lda * 2));
+    const u32x4 rA = buf_rsrc(P.A, (uint32_t)((int64_t)P.M * P.lda * 2));
     uint32_t lcq[RQ];                              // logical chunk of this lane in row group q of a tile
 #pragma unroll
     for (int q = 0; q < RQ; ++q) lcq[q] = (uint32_t)(((l & 7) ^ (((q & 1) << 2) | (rsub >> 1))) * 16);
@@ -66,9 +66,9 @@ __global__ __launch_bounds__(KwCfg<AR>::WAVES * 64, 1) void gemm_k192_kernel(KwP
 #pragma unroll
         for (int q = 0; q < RQ; ++q) {
             const int m = m0 + 8 * q + rsub;
-            const uint32_t voff = m < P.M ? (uint32_t)((int64_t)m * P.lda * 2) + lcq[q] : G_OOB;
+            const uint32_t voff = m < P.M ? (uint32_t)((int64_t)m * P.lda * 2) + lcq[q] : BUF_OOB;
 #pragma unroll
-            for (int kt = 0; kt < KW_KT; ++kt) g_load_lds16(voff, rA, abase + (uint32_t)(kt * KW_AKT + q * 1024), (uint32_t)kt * 128u);
+            for (int kt = 0; kt < KW_KT; ++kt) lds_load16(voff, rA, abase + (uint32_t)(kt * KW_AKT + q * 1024), (uint32_t)kt * 128u);
         }
     };
     // this lane's bias entries: columns n0 + 16 j + 4 g .. + 3
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(KwCfg<AR>::WAVES * 64, 1) void gemm_k192_kernel(KwP
     for (int j = 0; j < 12; ++j) braw[j] = P.bias ? *reinterpret_cast<const u32x2*>(P.bias + n0 + 16 * j + 4 * g) : u32x2{0u, 0u};
     int tile = wave_rank;
     if (tile < K.row_tiles) issue_a(tile);
-    g_vmcnt<0>();
+    wait_vmcnt<0>();
     __syncthreads();                               // the panel (and every wave's first tile) is in LDS
 
     const int swz = (c >> 1) & 7;
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(KwCfg<AR>::WAVES * 64, 1) void gemm_k192_kernel(KwP
         // the tile's images have been read: the next tile's operands fly under this tile's read-out
         const int m0 = tile * KW_AROWS;
         const int next = tile + wave_count;
-        g_lgkm0();
+        wait_lgkm0();
         if (next < K.row_tiles) issue_a(next);
         // ---- read-out, one 16-row half at a time: bias, bf16, 8-column chunks (lane groups g and g ^ 1 exchange one 4-column piece per
         // column-tile pair), the tail's operands of the half requested together, then the tails
@@ -178,8 +178,8 @@ __global__ __launch_bounds__(KwCfg<AR>::WAVES * 64, 1) void gemm_k192_kernel(KwP
         // the next tile's operands must have landed; this tile's stores, issued behind them (the counter retires in order), need not:
         // a full tile issues a known number of them
         constexpr int NST = (MC == 1 || MC == 4) ? RI * 6 : MC == 2 ? RI * 12 : -1;
-        if (NST >= 0 && m0 + KW_AROWS <= P.M) g_vmcnt<(NST >= 0 ? NST : 0)>();
-        else g_vmcnt<0>();
+        if (NST >= 0 && m0 + KW_AROWS <= P.M) wait_vmcnt<(NST >= 0 ? NST : 0)>();
+        else wait_vmcnt<0>();
     }
 }
 

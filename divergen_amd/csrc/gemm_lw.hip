@@ -64,17 +64,14 @@ template <int BM, int BN, int NSA_, int NSB_> struct LwCfg {
 };
 constexpr int LW_THREADS = 768, LW_MFMA_THREADS = 512;
 
-// lgkmcnt(0) as the BUILTIN: the compiler's wait-count pass sees it, so the fragment reads issued behind the barrier are waited for
-// with their own counts (behind an inline-asm wait it re-waits lgkmcnt(0) in front of the first MFMA of the phase)
-__device__ __forceinline__ void lw_lgkm0() { __builtin_amdgcn_s_waitcnt(0xc07f); }
-__device__ __forceinline__ uint32_t lw_sgpr(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+// (LDS reads are waited for with wait_lgkm0_tracked, the builtin: lds_direct.h says why)
 // s_waitcnt vmcnt(n') with the largest n' <= n out of {PRO, STEADY, STEP, 0}
 template <int PRO, int STEADY, int STEP>
 __device__ __forceinline__ void lw_vmcnt_le(int n) {
-    if (PRO > STEADY && n >= PRO) g_vmcnt<PRO>();
-    else if (STEADY > 0 && n >= STEADY) g_vmcnt<STEADY>();
-    else if (STEP > 0 && STEP < STEADY && n >= STEP) g_vmcnt<STEP>();
-    else g_vmcnt<0>();
+    if (PRO > STEADY && n >= PRO) wait_vmcnt<PRO>();
+    else if (STEADY > 0 && n >= STEADY) wait_vmcnt<STEADY>();
+    else if (STEP > 0 && STEP < STEADY && n >= STEP) wait_vmcnt<STEP>();
+    else wait_vmcnt<0>();
 }
 // one work item of the launch: output tile + K range
 struct LwItem { int m0, n0, kt0, NT, split; };
@@ -136,12 +133,12 @@ __global__ __launch_bounds__(LW_THREADS) void gemm_lw_kernel(GemmP P0) {
         const int rsub = l >> 3;
         const int lc = (l & 7) ^ (((lw & 1) << 2) | (rsub >> 1));     // row group q = lw + 4 s: (q & 1) == (lw & 1)
         const bool kt_ok = lc * 8 < ktail;
-        const uint32_t ldsq = lw_sgpr(lds0 + 1024u * lw);
+        const uint32_t ldsq = to_sgpr(lds0 + 1024u * lw);
         GemmP P = P0;
         LwItem it;
         uint32_t voffA[NLA], voffB[NLB];
         u32x4 rA;
-        const u32x4 rB = g_rsrc(P0.B, (uint32_t)((int64_t)P0.N * P0.ldb * 2));
+        const u32x4 rB = buf_rsrc(P0.B, (uint32_t)((int64_t)P0.N * P0.ldb * 2));
         auto setup = [&](int L0) {
             locate_item(L0, P, it);
 #pragma unroll
@@ -149,10 +146,10 @@ __global__ __launch_bounds__(LW_THREADS) void gemm_lw_kernel(GemmP P0) {
 #pragma unroll
             for (int s = 0; s < NLB; ++s) {
                 const int n = it.n0 + 8 * (lw + 4 * s) + rsub;
-                voffB[s] = n < P.N ? (uint32_t)(((int64_t)n * P.ldb + lc * 8) * 2) : G_OOB;
+                voffB[s] = n < P.N ? (uint32_t)(((int64_t)n * P.ldb + lc * 8) * 2) : BUF_OOB;
             }
-            const u32x4 r = g_rsrc(P.A, (uint32_t)((P.conv_kc ? (int64_t)P.cmap_n * (P.cmap_h + 2) * P.conv_wp + 2 * P.conv_wp + 2 : (int64_t)P.M) * P.lda * 2));
-            rA = u32x4{lw_sgpr(r[0]), lw_sgpr(r[1]), lw_sgpr(r[2]), lw_sgpr(r[3])};
+            const u32x4 r = buf_rsrc(P.A, (uint32_t)((P.conv_kc ? (int64_t)P.cmap_n * (P.cmap_h + 2) * P.conv_wp + 2 * P.conv_wp + 2 : (int64_t)P.M) * P.lda * 2));
+            rA = u32x4{to_sgpr(r[0]), to_sgpr(r[1]), to_sgpr(r[2]), to_sgpr(r[3])};
         };
         auto issue_a = [&](int t) {
             if (t >= it.NT) return;
@@ -161,7 +158,7 @@ __global__ __launch_bounds__(LW_THREADS) void gemm_lw_kernel(GemmP P0) {
             const bool tail = (kta == NTK - 1) && (ktail != GBK) && !kt_ok;
             const uint32_t dst = ldsq + a_slot(t % NSA);
 #pragma unroll
-            for (int s = 0; s < NLA; ++s) g_load_lds16(tail ? G_OOB : voffA[s], rA, lw_sgpr(dst + 4096u * s), lw_sgpr(soffA));
+            for (int s = 0; s < NLA; ++s) lds_load16(tail ? BUF_OOB : voffA[s], rA, to_sgpr(dst + 4096u * s), to_sgpr(soffA));
         };
         auto issue_b = [&](int t) {
             if (t >= it.NT) return;
@@ -170,7 +167,7 @@ __global__ __launch_bounds__(LW_THREADS) void gemm_lw_kernel(GemmP P0) {
             const bool tail = (kta == NTK - 1) && (ktail != GBK) && !kt_ok;
             const uint32_t dst = ldsq + B0 + (uint32_t)(t % NSB) * SBb;
 #pragma unroll
-            for (int s = 0; s < NLB; ++s) g_load_lds16(tail ? G_OOB : voffB[s], rB, lw_sgpr(dst + 4096u * s), lw_sgpr(soff));
+            for (int s = 0; s < NLB; ++s) lds_load16(tail ? BUF_OOB : voffB[s], rB, to_sgpr(dst + 4096u * s), to_sgpr(soff));
         };
         // loads of this wave that are younger than the later one of A(tau), B(tau) when tiles up to A(ia), B(ib) have been issued
         constexpr int STEADY = (NSA > NSB ? NSB - 1 : NSA - 2) * NLA + (NSB - 2) * NLB;
@@ -196,26 +193,26 @@ __global__ __launch_bounds__(LW_THREADS) void gemm_lw_kernel(GemmP P0) {
         for (int L0 = first; L0 < bound; L0 += nwx) {
             issue_a(NSA - 1);                      // second part of the prologue: the staging area is free
             wait_tile(0, NSA - 1, NSB - 1);
-            g_bar();                               // #0
+            wg_barrier();                               // #0
             const int NT = it.NT;
             for (int t = 0; t < NT; ++t) {
                 if (t >= 1) issue_b(t - 1 + NSB);  // I_{2t+1}
-                g_bar();                           // #(2t+1)
+                wg_barrier();                           // #(2t+1)
                 if (t >= 1) issue_a(t - 1 + NSA);  // I_{2t+2}
                 if (t + 1 < NT) wait_tile(t + 1, t - 1 + NSA, t - 1 + NSB);
-                g_bar();                           // #(2t+2)
+                wg_barrier();                           // #(2t+2)
             }
-            g_vmcnt<0>();
-            g_bar();                               // #(2 NT + 1): every slot is free
+            wait_vmcnt<0>();
+            wg_barrier();                               // #(2 NT + 1): every slot is free
             if (L0 + nwx < bound) {                // the next tile's first K-tiles land during the read-out
                 setup(L0 + nwx);
                 prologue_1();
             }
             if (P0.splits == 1) {                  // the read-out's barriers (the MFMA waves do the work)
-                if (P0.mode == 3) g_bar();
+                if (P0.mode == 3) wg_barrier();
 #pragma unroll
-                for (int p = 0; p < NPASS; ++p) { g_bar(); g_bar(); }
-                if constexpr ((MC == 3 || MC == 6) && Cfg::TOK0 < Cfg::RING) g_bar();      // the row table inside the last A slot has been read
+                for (int p = 0; p < NPASS; ++p) { wg_barrier(); wg_barrier(); }
+                if constexpr ((MC == 3 || MC == 6) && Cfg::TOK0 < Cfg::RING) wg_barrier();      // the row table inside the last A slot has been read
             }
         }
         return;
@@ -278,18 +275,18 @@ __global__ __launch_bounds__(LW_THREADS) void gemm_lw_kernel(GemmP P0) {
             }
             __builtin_amdgcn_s_setprio(0);
         };
-        g_bar();                                   // #0
+        wg_barrier();                                   // #0
         DGX_CLK(1);
-        if (grp == 1) g_bar();                     // #1: one phase behind group 0
+        if (grp == 1) wg_barrier();                     // #1: one phase behind group 0
         for (int t = 0; t < NT; ++t) {
             read_phase(t);
-            lw_lgkm0();
-            g_bar();                               // group 0: #(2t+1), group 1: #(2t+2)
+            wait_lgkm0_tracked();
+            wg_barrier();                               // group 0: #(2t+1), group 1: #(2t+2)
             mfma_phase(t);
-            lw_lgkm0();
-            g_bar();                               // group 0: #(2t+2), group 1: #(2t+3)
+            wait_lgkm0_tracked();
+            wg_barrier();                               // group 0: #(2t+2), group 1: #(2t+3)
         }
-        if (grp == 0) g_bar();                     // #(2 NT + 1)
+        if (grp == 0) wg_barrier();                     // #(2 NT + 1)
         DGX_CLK(2);
 
         // ---- split-K: the raw fp32 accumulators go to this split's slab; gemm_nt's fold kernel finishes the job
@@ -316,8 +313,8 @@ __global__ __launch_bounds__(LW_THREADS) void gemm_lw_kernel(GemmP P0) {
         constexpr int ITERS = (NCH + LW_MFMA_THREADS - 1) / LW_MFMA_THREADS;
         if (P.mode == 3) {
             if (tid < BM) g_fill_rowtok(P, rowtok, m0, tid);
-            lw_lgkm0();
-            g_bar();
+            wait_lgkm0_tracked();
+            wg_barrier();
         }
         int tid_e = tid;
         asm volatile("" : "+v"(tid_e));            // opaque: keeps the chunk addresses of the tail from being formed above the main loop
@@ -422,16 +419,16 @@ __global__ __launch_bounds__(LW_THREADS) void gemm_lw_kernel(GemmP P0) {
                     for (int j = 0; j < WNF; ++j) *reinterpret_cast<DGX_LDS u32x2*>(stg + row * SROW + (colw + 16 * j) * 2) = pk[i][j];
                 }
             }
-            lw_lgkm0();
-            g_bar();                               // slab staged
+            wait_lgkm0_tracked();
+            wg_barrier();                               // slab staged
             u32x4 yv[ITERS];
 #pragma unroll
             for (int k = 0; k < ITERS; ++k) {
                 const int idx = tid_e + k * LW_MFMA_THREADS, row = idx / CPR, ch = idx - row * CPR;
                 yv[k] = *reinterpret_cast<DGX_LDS const u32x4*>(stg + (idx < NCH ? row * SROW + ch * 16 : 0));
             }
-            lw_lgkm0();
-            g_bar();                               // slab read back: the staging area is free for the next one
+            wait_lgkm0_tracked();
+            wg_barrier();                               // slab read back: the staging area is free for the next one
 #pragma unroll
             for (int k = 0; k < ITERS; ++k) {
                 int row, ch, gm, gn;
@@ -446,7 +443,7 @@ __global__ __launch_bounds__(LW_THREADS) void gemm_lw_kernel(GemmP P0) {
         // the loaders' `issue_a(NSA - 1)` for the NEXT item would overwrite it while `locate` above still reads it for the last slab
         // (a garbage token = a store far outside the tensor: found by tests/test_gpu_pins.py with dgx_set_reserved_cus(16), the first
         // configuration that gives a 128 x 192 residual launch a second item per workgroup).  One more barrier per item, this layout only.
-        if constexpr ((MC == 3 || MC == 6) && Cfg::TOK0 < Cfg::RING) { lw_lgkm0(); g_bar(); }
+        if constexpr ((MC == 3 || MC == 6) && Cfg::TOK0 < Cfg::RING) { wait_lgkm0_tracked(); wg_barrier(); }
         DGX_CLK(4);
     }
 }

@@ -86,11 +86,11 @@ __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
 #pragma unroll
     for (int s = 0; s < NB; ++s) {
         const int n = n0 + 8 * (w + 8 * s) + rsub;
-        voffB[s] = n < P.N ? (uint32_t)(((int64_t)n * P.ldb + lc * 8) * 2) : G_OOB;
+        voffB[s] = n < P.N ? (uint32_t)(((int64_t)n * P.ldb + lc * 8) * 2) : BUF_OOB;
     }
     const bool kt_ok = lc * 8 < ktail;             // this lane's chunk exists in the last K-tile
-    const u32x4 rA = g_rsrc(P.A, (uint32_t)((P.conv_kc ? (int64_t)P.cmap_n * (P.cmap_h + 2) * P.conv_wp + 2 * P.conv_wp + 2 : (int64_t)P.M) * P.lda * 2));
-    const u32x4 rB = g_rsrc(P.B, (uint32_t)((int64_t)P.N * P.ldb * 2));
+    const u32x4 rA = buf_rsrc(P.A, (uint32_t)((P.conv_kc ? (int64_t)P.cmap_n * (P.cmap_h + 2) * P.conv_wp + 2 * P.conv_wp + 2 : (int64_t)P.M) * P.lda * 2));
+    const u32x4 rB = buf_rsrc(P.B, (uint32_t)((int64_t)P.N * P.ldb * 2));
     const uint32_t lds0 = (uint32_t)(uintptr_t)(DGX_LDS unsigned char*)lds_raw;
     const uint32_t ldsw = __builtin_amdgcn_readfirstlane(lds0 + 1024u * w);
     // one of the NL loads of a tile: k < NA -> A rows, else B rows
@@ -99,8 +99,8 @@ __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
         const uint32_t soff = (uint32_t)kta * (GBK * 2), soffA = g_a_soff(P, kta);
         const uint32_t dst = ldsw + (uint32_t)stage * SB;
         const bool tail = (kta == NTK - 1) && (ktail != GBK) && !kt_ok;
-        if (k < NA) g_load_lds16(tail ? G_OOB : voffA[k], rA, dst + 8192u * k, soffA);
-        else g_load_lds16(tail ? G_OOB : voffB[k - NA], rB, dst + BM * 128 + 8192u * (k - NA), soff);
+        if (k < NA) lds_load16(tail ? BUF_OOB : voffA[k], rA, dst + 8192u * k, soffA);
+        else lds_load16(tail ? BUF_OOB : voffB[k - NA], rB, dst + BM * 128 + 8192u * (k - NA), soff);
     };
 
     // ---- MFMA role: wave tile = rows grp*BM/2 .. (+16 i + c), columns wc*BN/4 .. (+16 j + c); a fragment (16 rows, k-half kh)
@@ -158,9 +158,9 @@ __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
     auto wait_tile = [&](int tau) {
         int later = NT - 1 - tau;
         if (later > NS - 2) later = NS - 2;
-        if (NS >= 4 && later >= 2) g_vmcnt<2 * NL>();
-        else if (NS >= 3 && later >= 1) g_vmcnt<NL>();
-        else g_vmcnt<0>();
+        if (NS >= 4 && later >= 2) wait_vmcnt<2 * NL>();
+        else if (NS >= 3 && later >= 1) wait_vmcnt<NL>();
+        else wait_vmcnt<0>();
     };
 #pragma unroll
     for (int t = 0; t < NS; ++t)
@@ -171,12 +171,12 @@ __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
     {
         int later = NT - 1;
         if (later > NS - 1) later = NS - 1;
-        if (NS >= 4 && later >= 3) g_vmcnt<3 * NL>();
-        else if (NS >= 3 && later >= 2) g_vmcnt<2 * NL>();
-        else if (later >= 1) g_vmcnt<NL>();
-        else g_vmcnt<0>();
+        if (NS >= 4 && later >= 3) wait_vmcnt<3 * NL>();
+        else if (NS >= 3 && later >= 2) wait_vmcnt<2 * NL>();
+        else if (later >= 1) wait_vmcnt<NL>();
+        else wait_vmcnt<0>();
     }
-    g_bar();                                       // #0: tile 0 visible to everyone
+    wg_barrier();                                       // #0: tile 0 visible to everyone
     DGX_CLK(1);
     int rs = 0;                                    // stage of the tile being read
     // Group 0 issues in its LOAD phase, group 1 right AFTER its MFMAs (both in I_{2t+3} for tile t + 2 when NS = 2).
@@ -192,32 +192,32 @@ __global__ __launch_bounds__(512, MINW) void gemm_nt_kernel(GemmP P) {
             }
             load_phase(rs, ti, is);
             rs = rs + 1 == NS ? 0 : rs + 1;
-            g_lgkm0();
-            g_bar();                               // #(2t+1)
+            wait_lgkm0();
+            wg_barrier();                               // #(2t+1)
             mfmas();
             if (t + 1 < NT) wait_tile(t + 1);
-            g_bar();                               // #(2t+2)
+            wg_barrier();                               // #(2t+2)
         }
-        g_bar();                                   // group 1's last phase
+        wg_barrier();                                   // group 1's last phase
     } else {
         int is = 0;                                // tile t + NS goes where tile t was
-        g_bar();                                   // #1: one phase behind group 0
+        wg_barrier();                                   // #1: one phase behind group 0
         for (int t = 0; t < NT; ++t) {
             load_phase(rs, -1, 0);
             rs = rs + 1 == NS ? 0 : rs + 1;
-            g_lgkm0();
+            wait_lgkm0();
             if (t + 1 < NT) wait_tile(t + 1);
-            g_bar();                               // #(2t+2)
+            wg_barrier();                               // #(2t+2)
             mfmas();
             if (t + NS < NT) {
 #pragma unroll
                 for (int k = 0; k < NL; ++k) issue_one(k, t + NS, is);
             }
             is = is + 1 == NS ? 0 : is + 1;
-            g_bar();                               // #(2t+3)
+            wg_barrier();                               // #(2t+3)
         }
     }
-    g_vmcnt<0>();
+    wait_vmcnt<0>();
     DGX_CLK(2);
 
     // ---- split-K: the raw fp32 accumulators go to this split's slab; dgx's fold kernel finishes the job
@@ -466,7 +466,7 @@ extern "C" int dgx_dev_gemm_log(const char* path) {
     if (path && *path && !(g_gemm_log = fopen(path, "w"))) return DGX_ERR_BAD_ARG;
     return DGX_OK;
 }
-extern int g_dgx_dev_wgrad_lw;      // wgrad_lw.hip
+const dgxplan::DevKnobs& dgx_dev_knobs() { return g_dev; }      // wgrad256.hip reads wgrad_lw here
 extern "C" int dgx_dev_set(const char* key, int value) {          // tests and A/B tools only; the values: dgxplan::DevKnobs
     if (!key) return DGX_ERR_BAD_ARG;
     if (!strcmp(key, "gemm_lw")) g_dev.lw = value;
@@ -474,8 +474,8 @@ extern "C" int dgx_dev_set(const char* key, int value) {          // tests and A
     else if (!strcmp(key, "gemm_tile")) { g_dev.tile_bm = value / 1000; g_dev.tile_bn = value % 1000; }
     else if (!strcmp(key, "gemm_splitk")) g_dev.splitk = value;
     else if (!strcmp(key, "gemm_k192")) g_dev.k192 = value;
-    else if (!strcmp(key, "wgrad_lw")) g_dgx_dev_wgrad_lw = value;   // 1 plan, 0 never the loader-wave form, 2 always
-    else if (!strcmp(key, "reset")) { g_dev = dgxplan::DevKnobs(); g_dgx_dev_wgrad_lw = 1; }
+    else if (!strcmp(key, "wgrad_lw")) g_dev.wgrad_lw = value;
+    else if (!strcmp(key, "reset")) g_dev = dgxplan::DevKnobs();
     else return DGX_ERR_BAD_ARG;
     return DGX_OK;
 }

@@ -18,6 +18,7 @@ struct DevKnobs {
     int tile_bm = 0, tile_bn = 0;       // gemm_tile:   bm * 1000 + bn, 0 = plan
     int splitk = 0;     // gemm_splitk: 0 plan, >= 1 forced slab count
     int k192 = -1;      // gemm_k192:   -1 / 1 plan, 0 never the resident-panel kernel
+    int wgrad_lw = 1;   // wgrad_lw:    1 plan (wgrad_plan.h), 0 never the loader-wave weight-gradient form, 2 always
 };
 
 struct GemmProblem {

@@ -9,8 +9,8 @@
 //   stores, 32-byte row padding = conflict-free ds_read_b64_tr_b16 within a 16-lane group);
 //   double-buffered LDS (2 x 68 KiB), next stage prefetched into registers under the MFMAs.
 //   Partials go to a workspace; a second (also grouped) kernel folds them into the arena.
-#include "dgx_common.h"
-#include <type_traits>
+#include "lds_direct.h"
+#include "wgrad_plan.h"
 
 namespace {
 constexpr int T256 = 256;               // tile edge
@@ -40,22 +40,9 @@ struct Params256 {
     // multi-image convolution (dgx_conv3x3_wgrad_bias_multi): the M dimension of the nine tap problems runs over nimg zero-bordered
     // image pairs; slab s belongs to the last image with slab0 <= s and carries ITS pointers and tap shift
     int nimg;
-    struct Img { const uint16_t* dy; const uint16_t* x; int wp, M, slab0; } img[6];
+    struct Img { const uint16_t* dy; const uint16_t* x; int wp, M, slab0; } img[dgxplan::W_MAXIMG];
 };
 
-// 16 bytes per lane from a raw buffer straight into LDS (no staging registers): lane i of the wave lands at
-// lds_wave_base + 16*i.  Out-of-range lanes (voff >= num_records) do not touch memory.  The caller orders the
-// data with s_waitcnt vmcnt + barrier; the compiler does not track these loads.  soff: scalar byte offset, part of the range check on
-// gfx950 (tools/probes/soffset_probe.hip) -- the row offset of a stage travels there, no VALU add per load in a loop whose lone wave per
-// SIMD pays for every instruction next to its MFMAs.
-__device__ __forceinline__ void buffer_load_lds16(uint32_t voff, u32x4 rsrc, uint32_t lds_wave_base, uint32_t soff) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds" ::"v"(voff), "s"(rsrc), "s"(lds_wave_base), "s"(soff)
-                 : "memory");
-}
-__device__ __forceinline__ u32x4 make_rsrc(const void* base, uint32_t bytes) {
-    const uint64_t a = (uint64_t)base;
-    return u32x4{(uint32_t)a, (uint32_t)(a >> 32) & 0xffffu, bytes, 0x00020000u};
-}
 // MFMA with the accumulator pinned to the AGPR half of the register file: 256 accumulator registers + two
 // fragment sets do not fit the 256 architectural VGPRs, and left to itself the allocator shuttles accumulator
 // tiles between the two halves around every MFMA.  Each accumulator is touched once per 64 MFMAs, far beyond
@@ -69,7 +56,6 @@ __device__ __forceinline__ void mfma16_agpr(f32x4& c, bf16x8 a, bf16x8 b) {
 __device__ __forceinline__ void mfma16_vgpr(f32x4& c, bf16x8 a, bf16x8 b) {
     asm("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
 }
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 }  // namespace
 
 // LDS image of one operand stage: [32 rows (m)][256 columns] bf16, 512-byte rows, NO padding (a wave-wide
@@ -100,7 +86,7 @@ __global__ __launch_bounds__(256) void wgrad256_partial_kernel(Params256 P) {
         const int su = __builtin_amdgcn_readfirstlane(s), tap = __builtin_amdgcn_readfirstlane(pi);
         Params256::Img im = P.img[0];
 #pragma unroll
-        for (int k = 1; k < 6; ++k)
+        for (int k = 1; k < dgxplan::W_MAXIMG; ++k)
             if (k < P.nimg && su >= P.img[k].slab0) im = P.img[k];
         q.A = im.dy + (int64_t)(im.wp + 1) * q.Nn;                           // grid position 0 (behind the slack)
         q.B = im.x + (int64_t)((tap / 3) * im.wp + tap % 3) * q.Kk;          // position 0 shifted by tap - (wp + 1)
@@ -117,11 +103,10 @@ __global__ __launch_bounds__(256) void wgrad256_partial_kernel(Params256 P) {
     // row-in-pair l >> 5, physical chunk l & 31, i.e. logical chunk (l & 31) ^ ((row & 3) << 1), row & 3 = 2*(w&1) + (l>>5)
     const int rip = l >> 5;
     const int lc = (l & 31) ^ (((2 * (w & 1) + rip) & 3) << 1);
-    const uint32_t OOB = 0x80000000u;
-    const uint32_t vA = (n0 + 8 * lc < q.Nn) ? (uint32_t)(((2 * w + rip) * q.Nn + n0 + 8 * lc) * 2) : OOB;
-    const uint32_t vB = (k0 + 8 * lc < q.Kk) ? (uint32_t)(((2 * w + rip) * q.Kk + k0 + 8 * lc) * 2) : OOB;
-    const u32x4 rA = make_rsrc(q.A, (uint32_t)((int64_t)m_end * q.Nn * 2));   // rows >= m_end are out of range
-    const u32x4 rB = make_rsrc(q.B, (uint32_t)((int64_t)m_end * q.Kk * 2));
+    const uint32_t vA = (n0 + 8 * lc < q.Nn) ? (uint32_t)(((2 * w + rip) * q.Nn + n0 + 8 * lc) * 2) : BUF_OOB;
+    const uint32_t vB = (k0 + 8 * lc < q.Kk) ? (uint32_t)(((2 * w + rip) * q.Kk + k0 + 8 * lc) * 2) : BUF_OOB;
+    const u32x4 rA = buf_rsrc(q.A, (uint32_t)((int64_t)m_end * q.Nn * 2));   // rows >= m_end are out of range
+    const u32x4 rB = buf_rsrc(q.B, (uint32_t)((int64_t)m_end * q.Kk * 2));
     const uint32_t lds0 = (uint32_t)(uintptr_t)(DGX_LDS unsigned char*)lds_raw;
     const uint32_t ldsw = __builtin_amdgcn_readfirstlane(lds0 + 1024u * w);
     // one LDS-direct load (16 B per lane, 1 KiB per wave) of stage st: h = 0..3 -> A rows 8h.., h = 4..7 -> B rows 8(h-4)..
@@ -129,8 +114,8 @@ __global__ __launch_bounds__(256) void wgrad256_partial_kernel(Params256 P) {
         const uint32_t row0 = (uint32_t)(m_begin + st * BM256);
         const uint32_t dst = ldsw + (uint32_t)(st & (NB256 - 1)) * STB256;
         const int j = h & 3;
-        if (h < 4) buffer_load_lds16(vA, rA, dst + 4096u * j, (row0 + 8 * j) * (uint32_t)(q.Nn * 2));
-        else buffer_load_lds16(vB, rB, dst + OPB256 + 4096u * j, (row0 + 8 * j) * (uint32_t)(q.Kk * 2));
+        if (h < 4) lds_load16(vA, rA, dst + 4096u * j, (row0 + 8 * j) * (uint32_t)(q.Nn * 2));
+        else lds_load16(vB, rB, dst + OPB256 + 4096u * j, (row0 + 8 * j) * (uint32_t)(q.Kk * 2));
     };
     auto issue = [&](int st) {
 #pragma unroll
@@ -169,7 +154,7 @@ __global__ __launch_bounds__(256) void wgrad256_partial_kernel(Params256 P) {
     f32x4 bacc[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) bacc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    bf16x8 ones = {(short)0x3F80, (short)0x3F80, (short)0x3F80, (short)0x3F80, (short)0x3F80, (short)0x3F80, (short)0x3F80, (short)0x3F80};
+    bf16x8 ones = bf16_ones();
     asm volatile("" : "+v"(ones));                // kept in registers: rematerialised in front of the inline-asm MFMA it would be a VALU write the
                                                   // hazard recogniser cannot pair with its reader
     auto bias_mfmas = [&](const bf16x8 (&af)[8]) {
@@ -210,7 +195,7 @@ __global__ __launch_bounds__(256) void wgrad256_partial_kernel(Params256 P) {
     // their own rates; issued in bulk, the loads and reads fill their queues and stall the wave's MFMA issue.
     auto step = [&](int st, auto NSLOT, const bf16x8 (&caf)[8], const bf16x8 (&cbf)[8], bf16x8 (&naf)[8], bf16x8 (&nbf)[8]) {   // NSLOT = (st + 1) & 3
         wait_vmcnt<16>();                                      // own loads of stage st+1 done (st+2, st+3 may fly)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // own LDS reads of stage st done before its buffer is recycled
+        wait_lgkm0();                                          // own LDS reads of stage st done before its buffer is recycled
         __syncthreads();
 #pragma unroll
         for (int gq = 0; gq < 16; ++gq) {
@@ -232,8 +217,7 @@ __global__ __launch_bounds__(256) void wgrad256_partial_kernel(Params256 P) {
     issue(3);
     wait_vmcnt<24>();
     __syncthreads();
-    typedef std::integral_constant<int, 0> S0; typedef std::integral_constant<int, 1> S1;
-    typedef std::integral_constant<int, 2> S2; typedef std::integral_constant<int, 3> S3;
+    typedef ic<0> S0; typedef ic<1> S1; typedef ic<2> S2; typedef ic<3> S3;
     read_frags(S0{}, af0, bf0);
     int st = 0;
     for (; st + 4 <= nst; st += 4) {         // st = 0 (mod 4) here: the slots of the stages read ahead are static
@@ -357,66 +341,68 @@ __global__ __launch_bounds__(256) void wgrad256_reduce_kernel(Params256 P, int64
     }
 }
 
-// rows per workgroup R (multiple of BM256) such that sum_p tiles_p * ceil(M_p / R) fits one round of 256 workgroups
-static void plan256(const dgx_wgrad_problem* pr, int n, int* S, int* slab) {
-    int tiles[MAXP256], maxM = 0;
-    for (int i = 0; i < n; ++i) {
-        tiles[i] = ((pr[i].Nn + T256 - 1) / T256) * ((pr[i].Kk + T256 - 1) / T256);
-        if (pr[i].M > maxM) maxM = pr[i].M;
-    }
-    int R = BM256;
-    for (;; R += BM256) {
-        int64_t wgs = 0;
-        for (int i = 0; i < n; ++i) wgs += (int64_t)tiles[i] * ((pr[i].M + R - 1) / R);
-        if (wgs <= 256 || R >= maxM) break;
-    }
-    for (int i = 0; i < n; ++i) {
-        S[i] = (pr[i].M + R - 1) / R;
-        if (S[i] < 1) S[i] = 1;
-        int sl = (pr[i].M + S[i] - 1) / S[i];
-        slab[i] = (sl + BM256 - 1) / BM256 * BM256;
-    }
-}
-
-static int64_t ws_floats256(const dgx_wgrad_problem* pr, int n, const int* S, int64_t* off, int64_t* offb = nullptr) {
-    int64_t tot = 0;
-    for (int i = 0; i < n; ++i) {
-        if (off) off[i] = tot;
-        if (S[i] > 1) tot += (int64_t)S[i] * pr[i].Nn * pr[i].Kk;
-    }
-    for (int i = 0; i < n; ++i) {                  // partial column sums of the split problems that carry a bias gradient
-        if (offb) offb[i] = tot;
-        if (S[i] > 1 && pr[i].gb) tot += ((int64_t)S[i] * pr[i].Nn + 3) / 4 * 4;
-    }
-    return tot;
-}
+using dgxplan::WgradSplitPlan;
+static_assert(dgxplan::W_TILE == T256 && dgxplan::W_STAGE == BM256 && dgxplan::W_MAXP == MAXP256, "wgrad_plan.h restates these");
 
 // wgrad_lw.hip: the persistent loader-wave form for groups of many tiles (no M-split, no workspace)
-bool wgrad_lw_wants(const dgx_wgrad_problem* pr, int n);
 int wgrad_lw_launch(const dgx_wgrad_problem* pr, int n, float beta, hipStream_t st);
-constexpr int MAXP_GROUP = 32;           // problems per dgx_linear_wgrad_grouped call: <= 12 on the split-M form, <= 32 on the loader-wave form
+const dgxplan::DevKnobs& dgx_dev_knobs();      // gemm_nt.hip: dgx_dev_set
+constexpr int MAXP_GROUP = dgxplan::WL_MAXP;   // problems per dgx_linear_wgrad_grouped call: <= 12 on the split-M form, <= 32 on the loader-wave form
+
+// The one launch path of the split form (wgrad_plan.h decides; nothing here does): the plan's cut into the descriptor, the partial
+// kernel, then the reduce the plan names.  ldc: row stride of every gradient (0: a Linear's own Kk).  The caller has set P.nimg / P.img.
+static int launch256(const WgradSplitPlan& pl, const dgx_wgrad_problem* pr, int ldc, Params256& P, float beta, void* workspace, hipStream_t st) {
+    if (pl.ws_floats > 0 && !workspace) return DGX_ERR_BAD_ARG;      // a split plan without a buffer to fold through
+    P.n = pl.n; P.beta = beta;
+    P.total = pl.total; P.per_xcd = pl.per_xcd; P.interleave = pl.interleave;
+    for (int i = 0; i < pl.n; ++i) {
+        const dgx_wgrad_problem& p = pr[i];
+        const WgradSplitPlan::Prob& c = pl.p[i];
+        Prob256& q = P.p[i];
+        q.A = (const uint16_t*)p.dy; q.B = (const uint16_t*)p.x;     // (multi-image: patched per slab in the kernel)
+        q.C = p.gw; q.gb = p.gb;
+        q.wsb = (float*)workspace + c.wsb_off;
+        q.ws = (float*)workspace + c.ws_off;
+        q.M = p.M; q.Nn = p.Nn; q.Kk = p.Kk;
+        q.ldc = ldc ? ldc : p.Kk;
+        q.tiles_k = c.tiles_k; q.tiles = c.tiles; q.S = c.S; q.slab = c.slab; q.wg0 = c.wg0; q.red0 = c.red0;
+    }
+    for (int i = pl.n; i < MAXP256; ++i) P.p[i] = P.p[0];
+    const size_t sm = (size_t)NB256 * STB256;
+    static bool once = false;
+    if (!once) {
+        (void)hipFuncSetAttribute((const void*)wgrad256_partial_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
+        once = true;
+    }
+    hipLaunchKernelGGL(wgrad256_partial_kernel, dim3(8 * P.per_xcd), dim3(256), sm, st, P);
+    if (pl.reduce == dgxplan::W_RED_LPQ16)
+        hipLaunchKernelGGL(wgrad256_reduce_kernel<16>, dim3(pl.reduce_grid), dim3(256), 0, st, P, pl.red_total, pl.bias_blocks, pl.bias_cb);
+    else if (pl.reduce == dgxplan::W_RED_LPQ1)
+        hipLaunchKernelGGL(wgrad256_reduce_kernel<1>, dim3(pl.reduce_grid), dim3(256), 0, st, P, pl.red_total, pl.bias_blocks, pl.bias_cb);
+    DGX_LAUNCH_CHECK();
+    return DGX_OK;
+}
+
+// a group (ldc == 0) or the nine taps of one image (ldc = 9 Cin) on the split form
+static int wgrad_split_group(const dgx_wgrad_problem* problems, int ldc, int n, float beta, void* workspace, void* stream) {
+    if (n <= 0) return DGX_OK;
+    if (!problems || n > MAXP256) return DGX_ERR_BAD_ARG;
+    for (int i = 0; i < n; ++i) {
+        const dgx_wgrad_problem& p = problems[i];
+        if (!p.dy || !p.x || !p.gw || p.M <= 0 || p.Nn <= 0 || p.Kk <= 0 || (p.Nn & 7) || (p.Kk & 7)) return DGX_ERR_BAD_ARG;
+        if ((int64_t)p.M * p.Nn * 2 >= (1ll << 31) || (int64_t)p.M * p.Kk * 2 >= (1ll << 31)) return DGX_ERR_UNSUPPORTED;
+    }
+    Params256 P;
+    P.nimg = 0;
+    return launch256(dgxplan::plan_wgrad_split(problems, n, ldc != 0), problems, ldc, P, beta, workspace, (hipStream_t)stream);
+}
 
 extern "C" int dgx_wgrad_grouped_form(const dgx_wgrad_problem* problems, int n) {
-    return problems && n > 0 && n <= MAXP_GROUP && wgrad_lw_wants(problems, n) ? 1 : 0;
-}
-
-// workspace of the split-M form for a group (what wgrad_grouped_impl writes): the ONLY place its size is computed
-static int64_t split_workspace_bytes(const dgx_wgrad_problem* problems, int n) {
-    if (!problems || n <= 0 || n > MAXP256) return 0;
-    int S[MAXP256], slab[MAXP256];
-    plan256(problems, n, S, slab);
-    return ws_floats256(problems, n, S, nullptr) * 4;
+    return problems && n > 0 && n <= MAXP_GROUP && dgxplan::wgrad_lw_wants(problems, n, dgx_dev_knobs()) ? 1 : 0;
 }
 extern "C" int64_t dgx_wgrad_grouped_workspace_bytes(const dgx_wgrad_problem* problems, int n) {
-    if (!problems || n <= 0 || n > MAXP_GROUP) return 0;
-    // a group the loader-wave form takes needs none -- unless its launch checks can still send it to the split-M form (n <= 12):
-    // then the split form's size is reported, so the fall-back in dgx_linear_wgrad_grouped never writes past the caller's buffer
-    if (wgrad_lw_wants(problems, n) && n > MAXP256) return 0;
-    return split_workspace_bytes(problems, n);
+    return dgxplan::wgrad_grouped_workspace_floats(problems, n) * 4;
 }
-
-static int wgrad_grouped_impl(const dgx_wgrad_problem* problems, const int* ldc, int n, float beta, void* workspace, void* stream);
-
 extern "C" int dgx_linear_wgrad_grouped(const dgx_wgrad_problem* problems, int n, float beta, void* workspace,
                                         void* stream) {
     double fl = 0.0, by = 0.0;
@@ -426,240 +412,111 @@ extern "C" int dgx_linear_wgrad_grouped(const dgx_wgrad_problem* problems, int n
         by += 2.0 * problems[i].M * ((double)problems[i].Nn + problems[i].Kk) + 8.0 * problems[i].Nn * problems[i].Kk;
     }
     DgxProfScope prof(DGX_PROF_WGRAD, stream, fl, by);
-    if (wgrad_lw_wants(problems, n)) {
+    if (dgxplan::wgrad_lw_wants(problems, n, dgx_dev_knobs())) {
         const int rc = wgrad_lw_launch(problems, n, beta, (hipStream_t)stream);
         if (rc == DGX_OK) { DGX_LAUNCH_CHECK(); return DGX_OK; }
-        if (rc != DGX_ERR_UNSUPPORTED || n > MAXP256) return rc;      // an operand over 2^31 bytes, ...: the split-M form takes <= 12 problems
+        if (rc != DGX_ERR_UNSUPPORTED || !dgxplan::wgrad_lw_may_fall_back(n)) return rc;      // an operand over 2^31 bytes, ...
     }
-    return wgrad_grouped_impl(problems, nullptr, n, beta, workspace, stream);
+    return wgrad_split_group(problems, 0, n, beta, workspace, stream);
+}
+
+// The single-problem entry points of the family: a one-problem call of the grouped path (the 128 x 128 split-M kernel they once ran
+// is retired; the summation order is the grouped path's).
+extern "C" int64_t dgx_wgrad_workspace_bytes(int M, int Nn, int Kk) { return dgxplan::wgrad_single_workspace_floats(M, Nn, Kk) * 4; }
+extern "C" int dgx_linear_wgrad(const void* dy, const void* x, float* gw, int M, int Nn, int Kk, float beta,
+                                void* workspace, void* stream) {
+    if (M <= 0 || Nn <= 0 || Kk <= 0) return DGX_OK;
+    if (!dy || !x || !gw || !workspace || (Nn & 7) || (Kk & 7) || ((int64_t)Nn * Kk & 3)) return DGX_ERR_BAD_ARG;
+    const dgx_wgrad_problem p = {dy, x, gw, M, Nn, Kk, nullptr};
+    return dgx_linear_wgrad_grouped(&p, 1, beta, workspace, stream);
 }
 
 // Weight gradient of a 3x3 convolution (pad 1, stride 1) without a column matrix: dW[co][tap][ci] = sum over the padded grid of
 // dypad[m][co] * xpad[m + shift(tap)][ci] -- nine Linear-type problems over the SAME two zero-bordered images (dgx_conv3x3_pad:
-// border rows of dypad are zero, so border positions add nothing), the tap being a pointer offset; gw f32 (Cout, 3, 3, Cin).
-extern "C" int64_t dgx_conv3x3_wgrad_workspace_bytes(int N, int H, int W, int Cin, int Cout) {
-    dgx_wgrad_problem pr[9];
-    const int64_t Mp = (int64_t)N * (H + 2) * (W + 2);
-    for (int t = 0; t < 9; ++t) { pr[t].dy = pr[t].x = nullptr; pr[t].gw = nullptr; pr[t].gb = nullptr; pr[t].M = (int)Mp; pr[t].Nn = Cout; pr[t].Kk = Cin; }
-    return split_workspace_bytes(pr, 9);       // the tap problems always run on the split-M form (ldc = 9 Cin), whatever wgrad_lw_wants says
+// border rows of dypad are zero, so border positions add nothing), the tap being a pointer offset; gw f32 (Cout, 3, 3, Cin), so every
+// tap block has row stride 9 Cin.  The one builder of those problems: rows = N (H+2) (W+2) of the (first) image, wp = W + 2; null
+// images for the sizing calls.  The tap problems always run on the split form, whatever wgrad_lw_wants says.
+static void tap_problems(dgx_wgrad_problem (&pr)[9], const void* dypad, const void* xpad, float* gw, float* gb, int64_t rows, int wp,
+                         int Cin, int Cout) {
+    for (int t = 0; t < 9; ++t) {
+        pr[t].dy = dypad ? (const uint16_t*)dypad + (int64_t)(wp + 1) * Cout : nullptr;                     // grid position 0 (behind the slack)
+        pr[t].x = xpad ? (const uint16_t*)xpad + (int64_t)((t / 3) * wp + t % 3) * Cin : nullptr;           // position 0 shifted by tap - (wp + 1)
+        pr[t].gw = gw ? gw + (int64_t)t * Cin : nullptr;
+        pr[t].gb = t == 0 ? gb : nullptr;        // the bias gradient = column sums of dypad (its border rows are zero): once
+        pr[t].M = (int)rows; pr[t].Nn = Cout; pr[t].Kk = Cin;
+    }
 }
-extern "C" int dgx_conv3x3_wgrad_bias(const void* dypad, const void* xpad, float* gw, float* gb, int N, int H, int W, int Cin, int Cout,
-                                      float beta, void* workspace, void* stream);
-extern "C" int dgx_conv3x3_wgrad(const void* dypad, const void* xpad, float* gw, int N, int H, int W, int Cin, int Cout, float beta,
-                                 void* workspace, void* stream) {
-    return dgx_conv3x3_wgrad_bias(dypad, xpad, gw, nullptr, N, H, W, Cin, Cout, beta, workspace, stream);
-}
-extern "C" int64_t dgx_conv3x3_wgrad_bias_workspace_bytes(int N, int H, int W, int Cin, int Cout) {
+static int64_t pad_grid_rows(int N, int H, int W) { return (int64_t)N * (H + 2) * (W + 2); }
+
+static int64_t conv_workspace_bytes(int N, int H, int W, int Cin, int Cout, bool bias) {
     dgx_wgrad_problem pr[9];
-    const int64_t Mp = (int64_t)N * (H + 2) * (W + 2);
     float dummy;
-    for (int t = 0; t < 9; ++t) { pr[t].dy = pr[t].x = nullptr; pr[t].gw = nullptr; pr[t].gb = t == 0 ? &dummy : nullptr; pr[t].M = (int)Mp; pr[t].Nn = Cout; pr[t].Kk = Cin; }
-    return split_workspace_bytes(pr, 9);
+    tap_problems(pr, nullptr, nullptr, nullptr, bias ? &dummy : nullptr, pad_grid_rows(N, H, W), W + 2, Cin, Cout);
+    return dgxplan::plan_wgrad_split(pr, 9, true).ws_floats * 4;
 }
+extern "C" int64_t dgx_conv3x3_wgrad_workspace_bytes(int N, int H, int W, int Cin, int Cout) { return conv_workspace_bytes(N, H, W, Cin, Cout, false); }
+extern "C" int64_t dgx_conv3x3_wgrad_bias_workspace_bytes(int N, int H, int W, int Cin, int Cout) { return conv_workspace_bytes(N, H, W, Cin, Cout, true); }
+
 extern "C" int dgx_conv3x3_wgrad_bias(const void* dypad, const void* xpad, float* gw, float* gb, int N, int H, int W, int Cin, int Cout,
                                       float beta, void* workspace, void* stream) {
     if (N <= 0 || H <= 0 || W <= 0) return DGX_OK;
     if (!dypad || !xpad || !gw || (Cin & 7) || (Cout & 7)) return DGX_ERR_BAD_ARG;
-    const int64_t Mp = (int64_t)N * (H + 2) * (W + 2);
-    const int wp = W + 2;
+    const int64_t Mp = pad_grid_rows(N, H, W);
     dgx_wgrad_problem pr[9];
-    int ldc[9];
-    for (int t = 0; t < 9; ++t) {
-        pr[t].dy = (const uint16_t*)dypad + (int64_t)(wp + 1) * Cout;                          // grid position 0 (behind the slack)
-        pr[t].x = (const uint16_t*)xpad + (int64_t)((t / 3) * wp + t % 3) * Cin;               // position 0 shifted by tap - (wp + 1)
-        pr[t].gw = gw + (int64_t)t * Cin;
-        pr[t].gb = t == 0 ? gb : nullptr;        // the bias gradient = column sums of dypad (its border rows are zero): once
-        pr[t].M = (int)Mp; pr[t].Nn = Cout; pr[t].Kk = Cin;
-        ldc[t] = 9 * Cin;
-    }
+    tap_problems(pr, dypad, xpad, gw, gb, Mp, W + 2, Cin, Cout);
     // the nine taps share the two padded images; useful work = the H x W interior
     DgxProfScope prof(DGX_PROF_WGRAD, stream, 2.0 * N * H * W * 9.0 * Cin * Cout, 2.0 * Mp * ((double)Cin + Cout) + 8.0 * 9.0 * Cin * Cout);
-    return wgrad_grouped_impl(pr, ldc, 9, beta, workspace, stream);
+    return wgrad_split_group(pr, 9 * Cin, 9, beta, workspace, stream);
 }
-
-static int wgrad_grouped_impl(const dgx_wgrad_problem* problems, const int* ldc, int n, float beta, void* workspace, void* stream) {
-    if (n <= 0) return DGX_OK;
-    if (!problems || n > MAXP256) return DGX_ERR_BAD_ARG;
-    for (int i = 0; i < n; ++i) {
-        const dgx_wgrad_problem& p = problems[i];
-        if (!p.dy || !p.x || !p.gw || p.M <= 0 || p.Nn <= 0 || p.Kk <= 0 || (p.Nn & 7) || (p.Kk & 7)) return DGX_ERR_BAD_ARG;
-        if ((int64_t)p.M * p.Nn * 2 >= (1ll << 31) || (int64_t)p.M * p.Kk * 2 >= (1ll << 31)) return DGX_ERR_UNSUPPORTED;
-    }
-    int S[MAXP256], slab[MAXP256];
-    int64_t off[MAXP256], offb[MAXP256];
-    plan256(problems, n, S, slab);
-    if (ws_floats256(problems, n, S, off, offb) > 0 && !workspace) return DGX_ERR_BAD_ARG;      // a split plan without a buffer to fold through
-    Params256 P;
-    P.n = n;
-    P.beta = beta;
-    P.nimg = 0;
-    int wg = 0;
-    int64_t red = 0;
-    for (int i = 0; i < n; ++i) {
-        const dgx_wgrad_problem& p = problems[i];
-        Prob256& q = P.p[i];
-        q.A = (const uint16_t*)p.dy;
-        q.B = (const uint16_t*)p.x;
-        q.C = p.gw;
-        q.gb = p.gb;
-        q.wsb = (float*)workspace + offb[i];
-        q.ws = (float*)workspace + off[i];
-        q.M = p.M; q.Nn = p.Nn; q.Kk = p.Kk;
-        q.ldc = ldc ? ldc[i] : p.Kk;
-        q.tiles_k = (p.Kk + T256 - 1) / T256;
-        q.S = S[i];
-        q.slab = slab[i];
-        q.tiles = ((p.Nn + T256 - 1) / T256) * q.tiles_k;
-        q.wg0 = wg;
-        q.red0 = red;
-        wg += q.tiles * S[i];
-        if (S[i] > 1) red += (int64_t)p.Nn * p.Kk / 4;   // unsplit problems are finished by the GEMM kernel itself
-    }
-    for (int i = n; i < MAXP256; ++i) P.p[i] = P.p[0];
-    hipStream_t st = (hipStream_t)stream;
-    const size_t sm = (size_t)NB256 * STB256;
-    static bool once = false;
-    if (!once) {
-        (void)hipFuncSetAttribute((const void*)wgrad256_partial_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-        once = true;
-    }
-    P.total = wg;
-    P.interleave = 0;
-    if (ldc && n > 1) {                            // dgx_conv3x3_wgrad: same M / Nn / Kk for every tap
-        P.interleave = 1;
-        for (int i = 1; i < n; ++i)
-            if (P.p[i].tiles != P.p[0].tiles || P.p[i].S != P.p[0].S || P.p[i].M != P.p[0].M) P.interleave = 0;
-    }
-    P.per_xcd = (wg + 7) / 8;
-    hipLaunchKernelGGL(wgrad256_partial_kernel, dim3(8 * P.per_xcd), dim3(256), sm, st, P);
-    int bias_cb = 1, bias_blocks = 0;              // bias-gradient folds of the split problems ride in the reduce launch
-    {
-        int maxNn = 0;
-        for (int i = 0; i < n; ++i)
-            if (S[i] > 1 && problems[i].gb) maxNn = problems[i].Nn > maxNn ? problems[i].Nn : maxNn;
-        if (maxNn > 0) { bias_cb = (maxNn + 255) / 256; bias_blocks = bias_cb * n; }
-    }
-    if (red > 0 || bias_blocks > 0) {
-        int maxS = 1;
-        for (int i = 0; i < n; ++i) maxS = S[i] > maxS ? S[i] : maxS;
-        if (red > 0 && red <= 32768 && maxS >= 16) {   // small output, deep split: 16 lanes share the walk over the slabs
-            // (total4 * 16 is a multiple of 64, so the xor-shuffles never mix lanes of different quads with idle ones)
-            hipLaunchKernelGGL(wgrad256_reduce_kernel<16>, dim3((int)((red * 16 + 255) / 256) + bias_blocks), dim3(256), 0, st, P, red,
-                               bias_blocks, bias_cb);
-        } else {
-            const int grid = (int)((red + 255) / 256 < 8192 ? (red + 255) / 256 : 8192);
-            hipLaunchKernelGGL(wgrad256_reduce_kernel<1>, dim3(grid + bias_blocks), dim3(256), 0, st, P, red, bias_blocks, bias_cb);
-        }
-    }
-    DGX_LAUNCH_CHECK();
-    return DGX_OK;
+extern "C" int dgx_conv3x3_wgrad(const void* dypad, const void* xpad, float* gw, int N, int H, int W, int Cin, int Cout, float beta,
+                                 void* workspace, void* stream) {
+    return dgx_conv3x3_wgrad_bias(dypad, xpad, gw, nullptr, N, H, W, Cin, Cout, beta, workspace, stream);
 }
 
 // dW += sum over SEVERAL zero-bordered image pairs (dypad_i, xpad_i) of the same convolution -- the FPN levels under one CenterNet tower
 // layer, whose weights are shared -- in ONE partial launch + ONE reduce launch: the nine tap problems run over all images' rows, cut
-// into slabs of R rows that never straddle an image (R = the smallest multiple of 32 for which 9 x sum_i ceil(M_i / R) workgroups fit
-// one round of 256).  Round 2 / early round 3: one partial + one reduce launch PER image (the P5 - P7 levels: ~30 us of launches for
-// microseconds of work each).
-static int conv_multi_plan(const dgx_conv_wgrad_item* items, int n, int tiles, int* R_out, int* nsl, int* M) {
-    int maxM = 0;
-    for (int i = 0; i < n; ++i) {
-        M[i] = items[i].N * (items[i].H + 2) * (items[i].W + 2);
-        maxM = M[i] > maxM ? M[i] : maxM;
-    }
-    int R = BM256;
-    for (;; R += BM256) {
-        int64_t wgs = 0;
-        for (int i = 0; i < n; ++i) wgs += (int64_t)9 * tiles * ((M[i] + R - 1) / R);
-        if (wgs <= 256 || R >= maxM) break;
-    }
-    int S = 0;
-    for (int i = 0; i < n; ++i) { nsl[i] = (M[i] + R - 1) / R; S += nsl[i]; }
-    *R_out = R;
-    return S;
+// into slabs of R rows that never straddle an image (plan_wgrad_split with img_rows).  Round 2 / early round 3: one partial + one
+// reduce launch PER image (the P5 - P7 levels: ~30 us of launches for microseconds of work each).
+static WgradSplitPlan conv_multi_plan(const dgx_conv_wgrad_item* items, int n, float* gw, float* gb, int Cin, int Cout, dgx_wgrad_problem (&pr)[9], int (&M)[dgxplan::W_MAXIMG]) {
+    for (int i = 0; i < n; ++i) M[i] = (int)pad_grid_rows(items[i].N, items[i].H, items[i].W);
+    tap_problems(pr, items[0].dypad, items[0].xpad, gw, gb, M[0], items[0].W + 2, Cin, Cout);
+    return dgxplan::plan_wgrad_split(pr, 9, true, M, n);
 }
-
 extern "C" int64_t dgx_conv3x3_wgrad_bias_multi_workspace_bytes(const dgx_conv_wgrad_item* items, int n, int Cin, int Cout) {
-    if (!items || n <= 0 || n > 6) return 0;
+    if (!items || n <= 0 || n > dgxplan::W_MAXIMG) return 0;
     if (n == 1) return dgx_conv3x3_wgrad_bias_workspace_bytes(items[0].N, items[0].H, items[0].W, Cin, Cout);
-    int R, nsl[6], M[6];
-    const int tiles = ((Cout + T256 - 1) / T256) * ((Cin + T256 - 1) / T256);
-    const int S = conv_multi_plan(items, n, tiles, &R, nsl, M);
-    return ((int64_t)9 * S * Cout * Cin + ((int64_t)S * Cout + 3) / 4 * 4) * 4;
+    dgx_wgrad_problem pr[9];
+    int M[dgxplan::W_MAXIMG];
+    return conv_multi_plan(items, n, nullptr, nullptr, Cin, Cout, pr, M).ws_floats * 4;
 }
 
 extern "C" int dgx_conv3x3_wgrad_bias_multi(const dgx_conv_wgrad_item* items, int n, float* gw, float* gb, int Cin, int Cout, float beta,
                                             void* workspace, void* stream) {
     if (n <= 0) return DGX_OK;
     if (!items || !gw || !workspace || (Cin & 7) || (Cout & 7) || Cin <= 0 || Cout <= 0) return DGX_ERR_BAD_ARG;
-    if (n > 6) return DGX_ERR_UNSUPPORTED;
-    if (n == 1)                                    // (a single slab would be finished by the partial kernel itself: the per-image plan)
+    if (n > dgxplan::W_MAXIMG) return DGX_ERR_UNSUPPORTED;
+    if (n == 1)                                    // (a single slab would be finished by the partial kernel itself: the per-image plan,
+                                                   // whose slabs are balanced, not R-row -- another summation order)
         return dgx_conv3x3_wgrad_bias(items[0].dypad, items[0].xpad, gw, gb, items[0].N, items[0].H, items[0].W, Cin, Cout, beta, workspace,
                                       stream);
-    int R, nsl[6], M[6];
-    const int tiles_k = (Cin + T256 - 1) / T256, tiles = ((Cout + T256 - 1) / T256) * tiles_k;
     for (int i = 0; i < n; ++i) {
         if (!items[i].dypad || !items[i].xpad || items[i].N <= 0 || items[i].H <= 0 || items[i].W <= 0) return DGX_ERR_BAD_ARG;
-        const int64_t rows = (int64_t)items[i].N * (items[i].H + 2) * (items[i].W + 2) + 2 * (int64_t)(items[i].W + 3);
+        const int64_t rows = pad_grid_rows(items[i].N, items[i].H, items[i].W) + 2 * (int64_t)(items[i].W + 3);
         if (rows * Cout * 2 >= (1ll << 31) || rows * Cin * 2 >= (1ll << 31)) return DGX_ERR_UNSUPPORTED;
     }
-    const int S = conv_multi_plan(items, n, tiles, &R, nsl, M);
+    dgx_wgrad_problem pr[9];
+    int M[dgxplan::W_MAXIMG];
+    const WgradSplitPlan pl = conv_multi_plan(items, n, gw, gb, Cin, Cout, pr, M);
     Params256 P;
-    P.n = 9;
-    P.beta = beta;
     P.nimg = n;
-    int s0 = 0;
     double fl = 0.0, by = 8.0 * 9.0 * Cin * Cout;
     for (int i = 0; i < n; ++i) {
         P.img[i].dy = (const uint16_t*)items[i].dypad; P.img[i].x = (const uint16_t*)items[i].xpad;
-        P.img[i].wp = items[i].W + 2; P.img[i].M = M[i]; P.img[i].slab0 = s0;
-        s0 += nsl[i];
+        P.img[i].wp = items[i].W + 2; P.img[i].M = M[i]; P.img[i].slab0 = pl.slab0[i];
         fl += 2.0 * items[i].N * items[i].H * items[i].W * 9.0 * Cin * Cout;
         by += 2.0 * M[i] * ((double)Cin + Cout);
     }
-    for (int i = n; i < 6; ++i) P.img[i] = P.img[0];
-    float* ws = (float*)workspace;
-    const int64_t per = (int64_t)S * Cout * Cin;
-    int wg = 0;
-    int64_t red = 0;
-    for (int t = 0; t < 9; ++t) {
-        Prob256& q = P.p[t];
-        q.A = P.img[0].dy; q.B = P.img[0].x;       // patched per slab in the kernel
-        q.C = gw + (int64_t)t * Cin;
-        q.gb = t == 0 ? gb : nullptr;              // the bias gradient = column sums of dypad (its border rows are zero): once
-        q.wsb = ws + 9 * per;
-        q.ws = ws + (int64_t)t * per;
-        q.M = M[0]; q.Nn = Cout; q.Kk = Cin;
-        q.ldc = 9 * Cin;
-        q.tiles_k = tiles_k;
-        q.S = S;
-        q.slab = R;
-        q.tiles = tiles;
-        q.wg0 = wg;
-        q.red0 = red;
-        wg += tiles * S;
-        red += (int64_t)Cout * Cin / 4;
-    }
-    for (int i = 9; i < MAXP256; ++i) P.p[i] = P.p[0];
-    hipStream_t st = (hipStream_t)stream;
-    const size_t sm = (size_t)NB256 * STB256;
-    static bool once = false;
-    if (!once) {
-        (void)hipFuncSetAttribute((const void*)wgrad256_partial_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-        once = true;
-    }
-    P.total = wg;
-    P.interleave = 1;
-    P.per_xcd = (wg + 7) / 8;
+    for (int i = n; i < dgxplan::W_MAXIMG; ++i) P.img[i] = P.img[0];
     DgxProfScope prof(DGX_PROF_WGRAD, stream, fl, by);
-    hipLaunchKernelGGL(wgrad256_partial_kernel, dim3(8 * P.per_xcd), dim3(256), sm, st, P);
-    const int bias_cb = (Cout + 255) / 256, bias_blocks = gb ? bias_cb * 9 : 0;
-    if (red <= 32768 && S >= 16) {
-        hipLaunchKernelGGL(wgrad256_reduce_kernel<16>, dim3((int)((red * 16 + 255) / 256) + bias_blocks), dim3(256), 0, st, P, red, bias_blocks,
-                           bias_cb);
-    } else {
-        const int grid = (int)((red + 255) / 256 < 8192 ? (red + 255) / 256 : 8192);
-        hipLaunchKernelGGL(wgrad256_reduce_kernel<1>, dim3(grid + bias_blocks), dim3(256), 0, st, P, red, bias_blocks, bias_cb);
-    }
-    DGX_LAUNCH_CHECK();
-    return DGX_OK;
+    return launch256(pl, pr, 9 * Cin, P, beta, workspace, (hipStream_t)stream);
 }

@@ -30,10 +30,9 @@
 // blocks against 0.75 for the split-M form with its bias sums (profiles/r04_wgrad_lw_*).
 // The caller (layers/swin_block.py) queues the problems of ~7 blocks per launch so that the item count is a multiple of the CU count
 // to within a few percent (7 stage-2 blocks = 1 008 items = 3.94 rounds).
-#include "dgx_common.h"
-#include <stdlib.h>
+#include "lds_direct.h"
+#include "wgrad_plan.h"
 #include <string.h>
-#include <type_traits>
 
 namespace {
 constexpr int WL_TN = 256, WL_TK = 192;          // tile: Nn rows x Kk columns of the weight gradient
@@ -60,26 +59,6 @@ struct WlParams {
     float beta;
 };
 
-__device__ __forceinline__ void wl_load_lds16(uint32_t voff, u32x4 rsrc, uint32_t lds_addr, uint32_t soff) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds" ::"v"(voff), "s"(rsrc), "s"(lds_addr), "s"(soff)
-                 : "memory");
-}
-__device__ __forceinline__ u32x4 wl_rsrc(const void* base, uint32_t bytes) {
-    const uint64_t a = (uint64_t)base;
-    return u32x4{(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a), (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(a >> 32) & 0xffffu)),
-                 (uint32_t)__builtin_amdgcn_readfirstlane((int)bytes), 0x00020000u};
-}
-template <int N> __device__ __forceinline__ void wl_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void wl_bar() {
-    asm volatile("s_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ void wl_lgkm0() { __builtin_amdgcn_s_waitcnt(0xc07f); }
-__device__ __forceinline__ uint32_t wl_sgpr(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-template <int N> using wl_ic = std::integral_constant<int, N>;
-template <int N, int I = 0, typename F> __device__ __forceinline__ void wl_static_for(F&& f) {
-    if constexpr (I < N) { f(wl_ic<I>{}); wl_static_for<N, I + 1>(f); }
-}
 }  // namespace
 
 __global__ __launch_bounds__(WL_THREADS) void wgrad_lw_kernel(WlParams P) {
@@ -128,8 +107,7 @@ __global__ __launch_bounds__(WL_THREADS) void wgrad_lw_kernel(WlParams P) {
         const int rip = l >> 5;                                       // row inside the 2-row instruction
         // logical 16-byte chunk of this lane in instruction s: row = 8 s + 2 lw + rip, row & 3 = 2 (lw & 1) + rip, (row >> 3) & 1 = s & 1
         const int lc0 = (l & 31) ^ (((2 * (lw & 1) + rip) & 3) << 1), lc1 = lc0 ^ 8;
-        const uint32_t ldsq = wl_sgpr(lds0 + 1024u * lw);
-        const uint32_t OOB = 0x80000000u;
+        const uint32_t ldsq = to_sgpr(lds0 + 1024u * lw);
         WlProb q;
         int n0, k0, NH = 0;
         uint32_t va[4], vb[4];                     // byte offsets of this lane in the 4 instructions of the NEXT dY / X granule to issue
@@ -141,19 +119,19 @@ __global__ __launch_bounds__(WL_THREADS) void wgrad_lw_kernel(WlParams P) {
 #pragma unroll
             for (int s = 0; s < 4; ++s) {          // instruction s: rows 8 s + 2 lw + rip
                 const int lc = (s & 1) ? lc1 : lc0, row = 8 * s + 2 * lw + rip;
-                va[s] = (n0 + 8 * lc < q.Nn) ? (uint32_t)((row * q.Nn + n0 + 8 * lc) * 2) : OOB;
-                vb[s] = (8 * lc < WL_TK && k0 + 8 * lc < q.Kk) ? (uint32_t)((row * q.Kk + k0 + 8 * lc) * 2) : OOB;
+                va[s] = (n0 + 8 * lc < q.Nn) ? (uint32_t)((row * q.Nn + n0 + 8 * lc) * 2) : BUF_OOB;
+                vb[s] = (8 * lc < WL_TK && k0 + 8 * lc < q.Kk) ? (uint32_t)((row * q.Kk + k0 + 8 * lc) * 2) : BUF_OOB;
             }
             stepA = (uint32_t)(WL_GR * q.Nn * 2); stepB = (uint32_t)(WL_GR * q.Kk * 2);
             sa = 0; sb = 0;
-            rA = wl_rsrc(q.A, (uint32_t)((int64_t)q.M * q.Nn * 2));   // rows >= M are out of range: zeros
-            rB = wl_rsrc(q.B, (uint32_t)((int64_t)q.M * q.Kk * 2));
+            rA = buf_rsrc_uniform(q.A, (uint32_t)((int64_t)q.M * q.Nn * 2));   // rows >= M are out of range: zeros
+            rB = buf_rsrc_uniform(q.B, (uint32_t)((int64_t)q.M * q.Kk * 2));
         };
         // One granule = 4 instructions of this wave.  The row offset lives in the VECTOR offset so that rows >= M fall under the descriptor's
         // range check and arrive as zeros (granules behind the end of M are issued all the same: no memory traffic, and the load counts
         // the waits rely on stay fixed); lanes beyond the matrix width keep bit 31 set through the adds (M * width * 2 < 2^31)
-        auto issue_a1 = [&](int s) { wl_load_lds16(va[s], rA, wl_sgpr(ldsq + sa + 4096u * s), 0u); va[s] += stepA; };
-        auto issue_b1 = [&](int s) { wl_load_lds16(vb[s], rB, wl_sgpr(ldsq + WL_B0 + sb + 4096u * s), 0u); vb[s] += stepB; };
+        auto issue_a1 = [&](int s) { lds_load16(va[s], rA, to_sgpr(ldsq + sa + 4096u * s), 0u); va[s] += stepA; };
+        auto issue_b1 = [&](int s) { lds_load16(vb[s], rB, to_sgpr(ldsq + WL_B0 + sb + 4096u * s), 0u); vb[s] += stepB; };
         auto next_a = [&]() { sa = sa + WL_GB == WL_NGA * WL_GB ? 0u : sa + WL_GB; };
         auto next_b = [&]() { sb = (sb + WL_GB) & (WL_NGB * WL_GB - 1); };
         auto issue_a = [&]() {
@@ -176,7 +154,7 @@ __global__ __launch_bounds__(WL_THREADS) void wgrad_lw_kernel(WlParams P) {
 #pragma unroll
         for (int f = 0; f < 4; ++f)
             pf[f] = lds_opaque(reinterpret_cast<const uint16_t*>(lds_raw + (8 * g + x) * 512 + 16 * ((c16 >> 1) & 1) + 8 * (c16 & 1) + 32 * ((4 * lw + f) ^ x ^ ((g & 1) << 2))));
-        const bf16x8 ones = {(short)0x3F80, (short)0x3F80, (short)0x3F80, (short)0x3F80, (short)0x3F80, (short)0x3F80, (short)0x3F80, (short)0x3F80};
+        const bf16x8 ones = bf16_ones();
         f32x4 bacc[4];
         bf16x8 bfrag[4];
 #pragma unroll
@@ -197,15 +175,15 @@ __global__ __launch_bounds__(WL_THREADS) void wgrad_lw_kernel(WlParams P) {
             const bool do_bias = q.gb != nullptr && k0 == 0;
             // every slot is free here (barrier E of the previous item); issue order A0 X0 A1 X1 A2 X2 A3 X3 A4, then A(h+5) X(h+4) behind B_h
             issue_a(); issue_b(); issue_a(); issue_b(); issue_a(); issue_b(); issue_a(); issue_b(); issue_a();
-            wl_vmcnt<28>();                        // A0, X0 (7 granules younger)
-            wl_bar();                              // P: the MFMA waves read X(0) and the first dY(0) fragments
+            wait_vmcnt<28>();                        // A0, X0 (7 granules younger)
+            wg_barrier();                              // P: the MFMA waves read X(0) and the first dY(0) fragments
             sbias = 0;
             if (do_bias) bias_read();
             for (int h = 0; h < NH; ++h) {
                 // before B_h: dY(h+1), X(h+1).  Younger than X(h+1): h = 0: A2 X2 A3 X3 A4; h = 1: A3 X3 A4 A5 X4; h = 2: A4 A5 X4 A6 X5; later:
                 // the four granules issued behind B_(h-2) and B_(h-1)
-                if (h < 3) wl_vmcnt<20>(); else wl_vmcnt<16>();
-                wl_bar();                          // B_h
+                if (h < 3) wait_vmcnt<20>(); else wait_vmcnt<16>();
+                wg_barrier();                          // B_h
                 if (do_bias) {                     // dY(h)'s rows were read a half ago (their LDS latency hides behind the barrier)
 #pragma unroll
                     for (int s = 0; s < 4; ++s) { issue_a1(s); bias_fold(s); }
@@ -217,7 +195,7 @@ __global__ __launch_bounds__(WL_THREADS) void wgrad_lw_kernel(WlParams P) {
                     issue_b();
                 }
             }
-            wl_bar();                              // E: every read of this item's granules has fed its MFMA
+            wg_barrier();                              // E: every read of this item's granules has fed its MFMA
             if (do_bias) {                         // every row of the 16 x 16 result holds the column sums: lanes 0-15 own one entry per fragment
 #pragma unroll
                 for (int f = 0; f < 4; ++f) {
@@ -279,13 +257,13 @@ __global__ __launch_bounds__(WL_THREADS) void wgrad_lw_kernel(WlParams P) {
         // half at ring position U (granule h = U mod 12): bc = X(h) fragments (held), bn <- X(h+1)
         auto half = [&](auto U, const bf16x8 (&bc)[3], bf16x8 (&bn)[3]) {
             constexpr int u = decltype(U)::value, sa = u % WL_NGA, sa1 = (u + 1) % WL_NGA, sb1 = (u + 1) % WL_NGB;
-            wl_bar();                              // B_h
+            wg_barrier();                              // B_h
             __builtin_amdgcn_s_setprio(1);
-            wl_static_for<8>([&](auto I) {
+            static_for<8>([&](auto I) {
                 constexpr int i = decltype(I)::value, ip = i + PRE;
-                if constexpr (ip < 8) afr[ip & 3] = fragA(wl_ic<sa>{}, wl_ic<ip>{});
-                else afr[ip & 3] = fragA(wl_ic<sa1>{}, wl_ic<ip - 8>{});
-                if constexpr (i < 3) bn[i] = fragB(wl_ic<sb1>{}, wl_ic<i>{});
+                if constexpr (ip < 8) afr[ip & 3] = fragA(ic<sa>{}, ic<ip>{});
+                else afr[ip & 3] = fragA(ic<sa1>{}, ic<ip - 8>{});
+                if constexpr (i < 3) bn[i] = fragB(ic<sb1>{}, ic<i>{});
 #pragma unroll
                 for (int j = 0; j < 3; ++j) acc[i][j] = mfma16(bc[j], afr[i & 3], acc[i][j]);     // D[k'][n]^T: lane = 4 Kk columns of one Nn row
             });
@@ -300,23 +278,23 @@ __global__ __launch_bounds__(WL_THREADS) void wgrad_lw_kernel(WlParams P) {
             __builtin_amdgcn_sched_group_barrier(0x100, 2, 0); __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
             __builtin_amdgcn_s_setprio(0);
         };
-        wl_bar();                                  // P: dY(0), X(0) landed
-        wl_static_for<3>([&](auto J) { b0[decltype(J)::value] = fragB(wl_ic<0>{}, J); });
-        wl_static_for<PRE>([&](auto I) { afr[decltype(I)::value] = fragA(wl_ic<0>{}, I); });
+        wg_barrier();                                  // P: dY(0), X(0) landed
+        static_for<3>([&](auto J) { b0[decltype(J)::value] = fragB(ic<0>{}, J); });
+        static_for<PRE>([&](auto I) { afr[decltype(I)::value] = fragA(ic<0>{}, I); });
         for (int h = 0; h < NH; h += 12) {         // NH is even; both rings are back at slot 0 after 12 halves
-            half(wl_ic<0>{}, b0, b1); half(wl_ic<1>{}, b1, b0);
+            half(ic<0>{}, b0, b1); half(ic<1>{}, b1, b0);
             if (h + 2 >= NH) break;
-            half(wl_ic<2>{}, b0, b1); half(wl_ic<3>{}, b1, b0);
+            half(ic<2>{}, b0, b1); half(ic<3>{}, b1, b0);
             if (h + 4 >= NH) break;
-            half(wl_ic<4>{}, b0, b1); half(wl_ic<5>{}, b1, b0);
+            half(ic<4>{}, b0, b1); half(ic<5>{}, b1, b0);
             if (h + 6 >= NH) break;
-            half(wl_ic<6>{}, b0, b1); half(wl_ic<7>{}, b1, b0);
+            half(ic<6>{}, b0, b1); half(ic<7>{}, b1, b0);
             if (h + 8 >= NH) break;
-            half(wl_ic<8>{}, b0, b1); half(wl_ic<9>{}, b1, b0);
+            half(ic<8>{}, b0, b1); half(ic<9>{}, b1, b0);
             if (h + 10 >= NH) break;
-            half(wl_ic<10>{}, b0, b1); half(wl_ic<11>{}, b1, b0);
+            half(ic<10>{}, b0, b1); half(ic<11>{}, b1, b0);
         }
-        wl_bar();                                  // E
+        wg_barrier();                                  // E
         // ---- read-out: fp32 read-modify-write of the gradient straight from the accumulators (16 bytes per lane, 64-byte runs per row)
         const float beta = P.beta;
 #pragma unroll
@@ -336,12 +314,15 @@ __global__ __launch_bounds__(WL_THREADS) void wgrad_lw_kernel(WlParams P) {
     }
 }
 
-// The grouped launch.  Returns DGX_ERR_UNSUPPORTED when the group is not this kernel's kind (the caller falls back to wgrad256).
+static_assert(dgxplan::WL_TILE_N == WL_TN && dgxplan::WL_TILE_K == WL_TK && dgxplan::WL_MAXP == WL_MAXP, "wgrad_plan.h restates these");
+
+// The grouped launch (wgrad_plan.h decides whether a group comes here and lays out its items).  Returns DGX_ERR_UNSUPPORTED when the
+// group is not this kernel's kind (the caller falls back to wgrad256).  The only decision made here: the grid against the reserved CUs.
 int wgrad_lw_launch(const dgx_wgrad_problem* pr, int n, float beta, hipStream_t st) {
     if (n <= 0 || n > WL_MAXP) return DGX_ERR_UNSUPPORTED;
+    const dgxplan::WgradLwPlan pl = dgxplan::plan_wgrad_lw(pr, n);
     WlParams P;
     memset((void*)&P, 0, sizeof(P));
-    int items = 0;
     for (int i = 0; i < n; ++i) {
         const dgx_wgrad_problem& p = pr[i];
         if (!p.dy || !p.x || !p.gw || p.M <= 0 || (p.Nn & 7) || (p.Kk & 7)) return DGX_ERR_BAD_ARG;
@@ -349,13 +330,12 @@ int wgrad_lw_launch(const dgx_wgrad_problem* pr, int n, float beta, hipStream_t 
         WlProb& q = P.p[i];
         q.A = (const uint16_t*)p.dy; q.B = (const uint16_t*)p.x; q.C = p.gw; q.gb = p.gb;
         q.M = p.M; q.Nn = p.Nn; q.Kk = p.Kk; q.ldc = p.Kk;
-        q.tiles_k = (p.Kk + WL_TK - 1) / WL_TK;
-        q.item0 = items;
-        items += ((p.Nn + WL_TN - 1) / WL_TN) * q.tiles_k;
+        q.tiles_k = pl.tiles_k[i];
+        q.item0 = pl.item0[i];
     }
-    for (int i = 0; i < WL_MAXP; ++i) P.item0[i] = i < n ? P.p[i].item0 : 0x7fffffff;
-    P.n = n; P.total = items; P.beta = beta;
-    P.per_xcd = (items + 7) / 8;
+    for (int i = 0; i < WL_MAXP; ++i) P.item0[i] = pl.item0[i];
+    P.n = n; P.total = pl.total; P.beta = beta;
+    P.per_xcd = pl.per_xcd;
     static bool once = false;
     if (!once) {
         if (hipFuncSetAttribute((const void*)wgrad_lw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WL_LDS) != hipSuccess) return DGX_ERR_UNSUPPORTED;
@@ -367,21 +347,3 @@ int wgrad_lw_launch(const dgx_wgrad_problem* pr, int n, float beta, hipStream_t 
     hipLaunchKernelGGL(wgrad_lw_kernel, dim3(8 * wgx), dim3(WL_THREADS), WL_LDS, st, P);
     return DGX_OK;
 }
-
-// Is this group worth the persistent form?  Many tiles of the loader-wave kernel (>= 3/4 of a round of the chip) whose contraction is
-// long enough for the main loop to dominate, and whose item count fills whole rounds to >= 74 % (4 stage-2 blocks = 2.25 rounds still win).
-int g_dgx_dev_wgrad_lw = 1;      // dgx_dev_set("wgrad_lw", v): 1 = the plan below, 0 = never this form, 2 = always (tests / A-B tools)
-bool wgrad_lw_wants(const dgx_wgrad_problem* pr, int n) {
-    const int mode = g_dgx_dev_wgrad_lw;
-    if (!mode || n <= 0 || n > WL_MAXP) return false;
-    int items = 0;
-    for (int i = 0; i < n; ++i) {
-        if (pr[i].M < 1024) return false;
-        items += ((pr[i].Nn + WL_TN - 1) / WL_TN) * ((pr[i].Kk + WL_TK - 1) / WL_TK);
-    }
-    if (mode == 2) return true;
-    if (items < 192) return false;
-    const int rounds = (items + 255) / 256;
-    return (double)items / (256.0 * rounds) >= 0.74;
-}
-

@@ -548,7 +548,9 @@ int dgx_col2im3x3(const void* dcol, void* dx, int N, int H, int W, int C, int st
  * `grad_output.t().mm(input)` of nn.Linear's backward (call sites as dgx_window_attention_*: qkv /
  * proj / fc1 / fc2 of swintransformer.py:118-120,35-37, box_head.py fc1/fc2) where the GEMM library
  * runs the long-K transposed shape at a fraction of its rate.  Nn, Kk multiples of 8.
- * workspace: dgx_wgrad_workspace_bytes(M,Nn,Kk) bytes of device scratch. */
+ * workspace: dgx_wgrad_workspace_bytes(M,Nn,Kk) bytes of device scratch (never NULL).
+ * A one-problem call of dgx_linear_wgrad_grouped (below) since the 128x128 split-M kernel these two once ran was retired: the same
+ * contract, the grouped path's plan and therefore its fp32 summation order.  Nothing in the product calls them. */
 int64_t dgx_wgrad_workspace_bytes(int M, int Nn, int Kk);
 int dgx_linear_wgrad(const void* dy, const void* x, float* gw, int M, int Nn, int Kk, float beta,
                      void* workspace, void* stream);
@@ -652,7 +654,8 @@ int dgx_upsample2x_add_bwd(const void* g, void* gtop, int N, int H, int W, int C
  * gw (Nn,Kk) = beta*gw + dy^T x  and, when gb != NULL, the
  * layer's BIAS gradient gb (Nn) = beta*gb + column sums of dy from the same pass (the sum over rows autograd performs for the
  * bias; computed as dy^T 1 on fragments the kernel holds anyway -- ABI version 3 added the field).
- * Nn % 8 == 0, Kk % 8 == 0.  workspace: dgx_wgrad_grouped_workspace_bytes(problems, n) bytes. */
+ * Nn % 8 == 0, Kk % 8 == 0.  workspace: dgx_wgrad_grouped_workspace_bytes(problems, n) bytes.
+ * Form, slabs, reduce and workspace are decided in one place, csrc/wgrad_plan.h (host-only, checked without a GPU). */
 typedef struct dgx_wgrad_problem {
     const void* dy;   /* bf16 (M, Nn) row-major */
     const void* x;    /* bf16 (M, Kk) row-major */
@@ -1102,7 +1105,8 @@ typedef struct dgx_conv_item { const void* xpad; void* y; int N, H, W; } dgx_con
 int dgx_conv3x3_gemm_multi(const dgx_conv_item* items, int n, const void* w, const void* bias, int Cin, int Cout, int relu, void* stream);
 /* The weight (+ bias) gradient of ONE convolution accumulated over n <= 6 zero-bordered image pairs (output gradient, input) -- the FPN
  * levels under a shared tower layer -- in one partial + one reduce launch: gw (Cout, 3, 3, Cin) f32 = beta*gw + sum_i dW_i, gb likewise.
- * workspace: dgx_conv3x3_wgrad_bias_multi_workspace_bytes(...) bytes. */
+ * workspace: dgx_conv3x3_wgrad_bias_multi_workspace_bytes(...) bytes (the same whether or not gb is given).  n == 1 runs the
+ * per-image plan of dgx_conv3x3_wgrad_bias (balanced slabs); n > 1 cuts every image into slabs of one common row count. */
 typedef struct dgx_conv_wgrad_item { const void* dypad; const void* xpad; int N, H, W; } dgx_conv_wgrad_item;
 int64_t dgx_conv3x3_wgrad_bias_multi_workspace_bytes(const dgx_conv_wgrad_item* items, int n, int Cin, int Cout);
 int dgx_conv3x3_wgrad_bias_multi(const dgx_conv_wgrad_item* items, int n, float* gw, float* gb, int Cin, int Cout, float beta,

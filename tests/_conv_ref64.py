@@ -5,7 +5,7 @@ on the NHWC / OHWI layouts the kernels use (no torch.nn.functional convolution i
 test holds the kernels to (tests/test_gpu_conv_numerics.py), the case tables both test files use, and the mutants.  Plain torch on the
 CPU; no project kernel is called from here.  tests/test_host_conv_ref.py pins the restatements on torch's float64 convolutions and their
 autograd, shows that fp32 CPU evaluations of the contract (bf16 operands, fp32 accumulation in three orders, one rounding) stay inside
-every bound on every case, that every mutant leaves one, and that the plans in the tables are what gemm_plan.h / plan256 decide.
+every bound on every case, that every mutant leaves one, and that the plans in the tables are what gemm_plan.h / wgrad_plan.h decide.
 
 Every restatement returns (ref, A, n): the float64 value, the SAME contraction over absolute values, and the number of addends of an
 element in the kernel's contraction (all nine taps counted, + 1 for the bias or the beta * g0 term; for dW / db the padded row count
@@ -46,7 +46,7 @@ copies, im2col and the one-hot launches were bit-exact, and every launch ran the
 Case tables.  GEMM_ROWS: geometry (N, H, W, Cin, Cout) -> (bm, bn, splits with the 64 MB workspace) of the forward launch and, where
 Cout % 64 == 0 (the C ABI wants whole K-tiles), of the input-gradient launch (Cin and Cout exchanged); the form is 1 (loader-wave) by
 default and 0 with dgx_dev("gemm_lw", 0), splits = 1 without a workspace.  WGRAD_ROWS: geometry -> (S, 32-row stages per slab, reduce
-form) as `plan256` decides, restated in `wgrad_plan`.
+form) as csrc/wgrad_plan.h (plan_wgrad_split) decides, restated in `wgrad_plan`; tests/test_host_wgrad_plan.py holds the two together.
 
 Mutants: wrong restatements of the kind the kernels could produce (FWD_MUTANTS, WGRAD_MUTANTS, STRIDE2_MUTANTS; the text next to each).
 A mutant is DEFINED on a case when its float64 value differs from the restatement's at all; it must then leave the bound somewhere."""
@@ -123,6 +123,22 @@ WGRAD_ROWS = {
     (2, 52, 52, 64, 64): (27, 7, "lpq16"),          # 4k + 3
     (2, 56, 56, 64, 64): (27, 8, "lpq16"),          # 2 x 4
 }
+# Linear weight gradients (dgx_linear_wgrad_grouped): group of (M, Nn, Kk) -> ([S per problem], 32-row stages per slab of the LAST problem,
+# reduce form) as wgrad_plan.h decides, restated in `wgrad_group_plan`; each the smallest shape found that reaches its branch
+LINEAR_WGRAD_ROWS = {
+    ((32, 64, 72),): ([1], 1, "direct"),                          # S = 1: written direct with beta
+    ((1000, 64, 72),): ([32], 1, "lpq16"),
+    ((1000, 264, 8),): ([32], 1, "lpq16"),                        # two row tiles, Kk = 8
+    ((300, 64, 64),): ([10], 1, "lpq1"),                          # one lane per quad because S < 16
+    ((300, 512, 264),): ([10], 1, "lpq1"),                        # ... because the output exceeds 32 768 quads; ragged second column tile; two bias column blocks
+    ((32, 72, 264), (330, 72, 264)): ([1, 11], 1, "lpq1"),        # one unsplit and one split problem in one launch
+    ((4000, 264, 520),): ([42], 3, "lpq1"),                       # 96-row slabs: the odd-stage tail of the pipeline
+    ((2056, 264, 264),): ([33], 2, "lpq16"),                      # 2 stages, last slab 8 rows
+    ((4040, 264, 520),): ([32], 4, "lpq1"),                       # 4 stages, last slab 72 rows
+    ((5384, 264, 520),): ([34], 5, "lpq1"),                       # 5 stages, last slab 104 rows
+}
+# the loader-wave form, forced (dgx_dev wgrad_lw 2): 52 items, ragged contraction and tiles, n > 12 | one problem, one item
+LINEAR_WGRAD_LW = [((1064, 264, 200),) * 13, ((1024, 256, 192),)]
 WGRAD_MULTI_LEVELS = MULTI_LEVELS + [(2, 32, 32)]
 WGRAD_MULTI_WIDTHS = [(256, 256), (64, 8), (64, 264)]
 PAD_SHAPES = [(1, 1, 1, 8), (2, 5, 9, 64), (3, 7, 1, 264), (1, 1, 6, 72)]
@@ -206,7 +222,7 @@ def gemm_plan(M, Ncol, K, ws_bytes, tile=None, splitk=0):
 
 
 def wgrad_plan(N, H, W, Cin, Cout):
-    """plan256 for the nine tap problems of one image, restated: (S, slab rows, 32-row stages per slab, reduce form)"""
+    """wgrad_plan.h plan_wgrad_split for the nine tap problems of one image, restated: (S, slab rows, 32-row stages per slab, reduce form)"""
     Mp, tiles = N * (H + 2) * (W + 2), -(-Cout // 256) * -(-Cin // 256)
     R = 32
     while 9 * tiles * -(-Mp // R) > 256 and R < Mp:
@@ -217,13 +233,26 @@ def wgrad_plan(N, H, W, Cin, Cout):
     return S, slab, slab // 32, form
 
 
+def wgrad_group_plan(shapes):
+    """plan_wgrad_split for a group of Linear problems (M, Nn, Kk), restated: ([S], [slab rows], reduce form)"""
+    tiles = [-(-Nn // 256) * -(-Kk // 256) for _, Nn, Kk in shapes]
+    R = 32
+    while sum(t * -(-M // R) for t, (M, _, _) in zip(tiles, shapes)) > 256 and R < max(M for M, _, _ in shapes):
+        R += 32
+    S = [max(-(-M // R), 1) for M, _, _ in shapes]
+    slab = [-(-(-(-M // s)) // 32) * 32 for s, (M, _, _) in zip(S, shapes)]
+    red = sum(Nn * Kk // 4 for s, (_, Nn, Kk) in zip(S, shapes) if s > 1)
+    form = "direct" if red == 0 else "lpq16" if (red <= 32768 and max(S) >= 16) else "lpq1"
+    return S, slab, form
+
+
 def wgrad_workspace_floats(S, Cin, Cout):
-    """ws_floats256 for those problems (the first carries the bias gradient): nothing when S = 1"""
+    """the workspace of that plan (the first carries the bias gradient): nothing when S = 1"""
     return 0 if S == 1 else 9 * S * Cout * Cin + (S * Cout + 3) // 4 * 4
 
 
 def wgrad_multi_plan(levels, Cin, Cout):
-    """conv_multi_plan: (R, [slabs per image])"""
+    """plan_wgrad_split over several images: (R, [slabs per image])"""
     Ms, tiles = [n * (h + 2) * (w + 2) for n, h, w in levels], -(-Cout // 256) * -(-Cin // 256)
     R = 32
     while sum(9 * tiles * -(-m // R) for m in Ms) > 256 and R < max(Ms):

@@ -497,3 +497,82 @@ def test_python_arena_conv_accumulates_two_steps():
     (dW, db), _, _ = R.conv_wgrad64(dy, inp["x"], None, 0.0)
     two = {"dW": R.worst_ratio(prev[0], 2 * dW, total[0]), "db": R.worst_ratio(prev[1], 2 * db, total[1])}
     R.report("conv_ops.Conv2d(arena)", "%s twice-the-reference" % (geom,), two)
+
+
+# ------------------------------------------------------------------ Linear weight gradients (the same kernels, through dgx_linear_wgrad_grouped)
+@functools.lru_cache(maxsize=None)
+def linear_case(shapes):
+    """operands, first gradients and the float64 references of a group, computed once: [(dy, x, gw0, gb0, dW, Aw, db, Ab)]"""
+    gen = torch.Generator().manual_seed(7000 + sum(M + Nn + Kk for M, Nn, Kk in shapes))
+    out = []
+    for M, Nn, Kk in shapes:
+        dy, x = R.bf(torch.randn(M, Nn, generator=gen)), R.bf(torch.randn(M, Kk, generator=gen))
+        gw0, gb0 = torch.randn(Nn, Kk, generator=gen), torch.randn(Nn, generator=gen)
+        d, xx = dy.double(), x.double()
+        out.append((dy, x, gw0, gb0, d.t() @ xx, d.abs().t() @ xx.abs(), d.sum(0), d.abs().sum(0)))
+    return out
+
+
+def run_linear_group(shapes, expect_form, out):
+    from divergen_amd import _lib as L
+    lib = L.lib()
+    case = linear_case(shapes)
+    ops = [(dev(c[0]), dev(c[1])) for c in case]
+    for beta in (0.0, 1.0):
+        for with_gb in (True, False):
+            n = len(shapes)
+            arr = (L.WgradProblem * n)()
+            gws, gbs = [], []
+            for i, ((M, Nn, Kk), c, (dyd, xd)) in enumerate(zip(shapes, case, ops)):
+                gws.append(guarded(Nn * Kk, F32, c[2] if beta else None))
+                gbs.append(guarded(Nn, F32, c[3] if beta else None) if with_gb else None)
+                arr[i].dy, arr[i].x, arr[i].gw, arr[i].gb = L.ptr(dyd), L.ptr(xd), L.ptr(gws[i]), L.ptr(gbs[i])
+                arr[i].M, arr[i].Nn, arr[i].Kk = M, Nn, Kk
+            assert int(lib.dgx_wgrad_grouped_form(arr, n)) == expect_form
+            nws = max(int(lib.dgx_wgrad_grouped_workspace_bytes(arr, n)) // 4, 4)
+            ws = guarded(nws, F32)
+            assert lib.dgx_linear_wgrad_grouped(arr, n, beta, L.ptr(ws), L.stream()) == 0
+            torch.cuda.synchronize()
+            assert tail_ok(ws, nws), "dgx_linear_wgrad_grouped wrote behind its workspace"
+            for i, ((M, Nn, Kk), c) in enumerate(zip(shapes, case)):
+                assert tail_ok(gws[i], Nn * Kk) and (gbs[i] is None or tail_ok(gbs[i], Nn)), "dgx_linear_wgrad_grouped wrote behind a buffer"
+                dW, Aw, db, Ab, cnt = c[4], c[5], c[6], c[7], M
+                if beta:
+                    dW, Aw, db, Ab, cnt = dW + beta * c[2].double(), Aw + c[2].double().abs(), db + beta * c[3].double(), Ab + c[3].double().abs(), M + 1
+                key = "%sbeta%d%s" % ("p%d." % i if n > 1 else "", beta, "" if with_gb else ".nogb")
+                rw = R.worst_ratio(gws[i][:Nn * Kk].view(Nn, Kk).cpu(), dW, R.f32_bound(dW, Aw, cnt))
+                rb = R.worst_ratio(gbs[i][:Nn].cpu(), db, R.f32_bound(db, Ab, cnt)) if with_gb else 0.0
+                if i in (0, n - 1):
+                    out["dW." + key] = rw
+                    if with_gb:
+                        out["db." + key] = rb
+                else:                               # the inner problems of a long group: asserted, not printed one by one
+                    assert rw <= 1.0 and rb <= 1.0, (shapes, i, rw, rb)
+
+
+LINEAR_CASES = [("split", sh, 0) for sh in R.LINEAR_WGRAD_ROWS] + [("lw", sh, r) for sh in R.LINEAR_WGRAD_LW for r in (0, 16)]
+
+
+@pytest.mark.parametrize("form,shapes,reserved_cus", LINEAR_CASES, ids=lambda v: "%dx%s" % (len(v), v[0]) if isinstance(v, tuple) else str(v))
+def test_linear_wgrad_grouped_every_element(form, shapes, reserved_cus, dgx_dev):
+    """gw and gb of every problem of dgx_linear_wgrad_grouped against float64 under the fp32-accumulation bound, beta 0 / 1, with and
+    without bias gradients.  Split form: every branch of its plan (LINEAR_WGRAD_ROWS: unsplit, both reduce forms, 1-5 stages per slab with
+    ragged last slabs, a mixed group).  Loader-wave form, forced: 13 problems of 4 ragged items each (n > 12: no fall-back, no workspace)
+    and one problem of one exact item, with all CUs and with 16 reserved."""
+    from divergen_amd import _lib as L
+    out = {}
+    if form == "split":
+        S, stages, red = R.LINEAR_WGRAD_ROWS[shapes]
+        plan = R.wgrad_group_plan(shapes)
+        assert (plan[0], plan[1][-1] // 32, plan[2]) == (S, stages, red)
+        dgx_dev("wgrad_lw", 0)
+        run_linear_group(shapes, 0, out)
+        R.report("linear_wgrad_grouped", "%s S%s stages%d %s" % (shapes if len(shapes) > 1 else shapes[0], S, stages, red), out)
+    else:
+        dgx_dev("wgrad_lw", 2)
+        L.lib().dgx_set_reserved_cus(reserved_cus)
+        try:
+            run_linear_group(shapes, 1, out)
+        finally:
+            L.lib().dgx_set_reserved_cus(0)
+        R.report("linear_wgrad_grouped", "lw %d x %s reserved%d" % (len(shapes), shapes[0], reserved_cus), out)

@@ -911,7 +911,7 @@ def test_linear_wgrad_split_m(M, Nn, Kk):
     wgrad_into(acc, dy.to(DEV), x.to(DEV), 1.0)
     # bf16 products are exact in fp32; only the fp32 summation order differs: 1e-5 of the result scale
     assert (acc.cpu() - ref).abs().max() <= 2e-5 * ref.abs().max() + 1e-3
-    # the single-problem 128x128 kernel of the same ABI family (dgx_linear_wgrad) stays covered through the C ABI
+    # the single-problem entry point of the same ABI family (dgx_linear_wgrad: a one-problem call of the grouped path) through the C ABI
     from divergen_amd import _lib as L
     acc2, dyd, xd = acc0.to(DEV).clone(), dy.to(DEV), x.to(DEV)
     ws = torch.empty(L.lib().dgx_wgrad_workspace_bytes(M, Nn, Kk), dtype=torch.uint8, device=DEV)
@@ -1074,7 +1074,7 @@ def test_layernorm_bwd_emit_equals_the_two_kernel_path(xdt, gather, ews, eshift,
 @pytest.mark.parametrize("shapes", [
     [(8192, 768, 3072), (8192, 3072, 768), (10368, 768, 768), (10368, 2304, 768)],     # Swin-L stage 2 block
     [(100, 192, 264), (8192, 40, 768), (4000, 768, 776)],                                # ragged: partial stages / tiles
-    [(2048, 1536, 1536)],                                                                # unsplit (S == 1): direct epilogue
+    [(2048, 1536, 1536)],                                                                # 36 tiles: seven slabs of 320 rows
     [(33, 8, 8)],
 ])
 def test_linear_wgrad_grouped(shapes):

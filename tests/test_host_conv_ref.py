@@ -8,7 +8,7 @@ convolution kernels to.
 * every mutant puts at least one element outside its bound on every case on which it is defined (= differs from the restatement at all),
   judged through its worst element;
 * the implicit-GEMM plans of the table are what gemm_plan.h decides (tests/native/gemm_plan_check.cpp, with the 64 MB workspace and with
-  none, default form and gemm_lw = 0), and the restated plan256 reproduces every weight-gradient row."""
+  none, default form and gemm_lw = 0), and the restated weight-gradient plan (csrc/wgrad_plan.h) reproduces every weight-gradient row."""
 import functools
 import os
 import shutil

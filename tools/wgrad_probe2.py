@@ -13,4 +13,4 @@ for (M,K,N) in [(131072,192,576),(131072,192,768),(131072,768,192),(32768,384,11
     acc = torch.zeros(N,K,device=dev)
     fl = 2.0*M*K*N
     probe("M%d K%d N%d hipblaslt" % (M,K,N), lambda: torch.addmm(acc, gy.t(), x, out_dtype=torch.float32, out=acc), fl)
-    probe("   dgx_linear_wgrad", lambda: wgrad_into(acc, gy, x), fl)
+    probe("   dgx_linear_wgrad_grouped", lambda: wgrad_into(acc, gy, x), fl)
