@@ -129,6 +129,7 @@ SIGNATURES = {
     "dgx_self_copy_paste_all": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     "dgx_remove_background": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p]),
     "dgx_polygons_to_bitmask": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p]),
+    "dgx_resize_bilinear_u8": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_p, c_i, c_i64, c_p, c_i64, c_p, c_i64, c_p]),
     "dgx_self_copy_merge_workspace_words": (c_i64, [c_i, c_i, c_i, c_i]),
     "dgx_self_copy_merge": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     "dgx_im2col3x3": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),

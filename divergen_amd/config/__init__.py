@@ -177,6 +177,14 @@ def get_cfg():
     #   what the worker would have filled.  Built for INPUT.USE_COPY_METHOD 'none' / 'syn_copy'; the self-copy methods and
     #   INPUT.ACTIVE_SELECT are refused with it at start-up.  Off by default: the worker rasterises, as before.
     cfg.INPUT.DEVICE_RASTER = False
+    #   INPUT.DEVICE_RESIZE: the loader workers (training mapper only) skip both Pillow resizes.  A sample ships its decoded source image
+    #   with the numbers of its resize-crop-flip and the fixed-point coefficient tables of the crop window; an instance-pool patch whose
+    #   source has at most 4x the pixels of the resized patch ships its source crop.  The training process resizes on the device, one
+    #   launch per sample on the loader's side stream in front of everything that reads pixels (dgx_resize_bilinear_u8,
+    #   divergen_amd/csrc/resize_u8.hip), byte for byte Pillow's BILINEAR.  The np.random draws are unchanged.  Built for
+    #   INPUT.USE_COPY_METHOD 'none' / 'syn_copy'; the self-copy methods and INPUT.ACTIVE_SELECT are refused with it at start-up.
+    #   Off by default: the worker resizes, as before.
+    cfg.INPUT.DEVICE_RESIZE = False
     #   MODEL.ROI_BOX_HEAD.WS_PROP_SCORE: admits, with WITH_IMAGE_LABELS, MODEL.ROI_BOX_HEAD.IMAGE_LABEL_LOSS 'wsddn' / 'wsod' (the softmax
     #   over an image's proposals times the sigmoid class scores: dgx_wsddn_loss, divergen_amd/csrc/wsddn_loss.hip) and the predictor
     #   branch it reads, MODEL.ROI_BOX_HEAD.WITH_SOFTMAX_PROP (prop_score: Linear-ReLU-Linear, two more GEMMs per cascade stage of an

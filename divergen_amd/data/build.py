@@ -26,7 +26,7 @@ import os
 import numpy as np
 import torch
 
-from ..structures import BitMasks, Boxes, Instances, PolygonCrossings
+from ..structures import BitMasks, Boxes, DeviceResizeImage, Instances, PolygonCrossings
 from ..utils import comm
 from .samplers import RepeatFactorTrainingSampler, TrainingSampler
 
@@ -469,8 +469,38 @@ class DatasetMapper:
         self.use_instance_mask = cfg.MODEL.MASK_ON
         # INPUT.DEVICE_RASTER: the training samples carry their polygons' crossing lists instead of dense masks
         self.device_raster = bool(cfg.INPUT.get("DEVICE_RASTER", False)) and is_train
+        # INPUT.DEVICE_RESIZE: the training samples carry the decoded source and the resize job instead of the mapped image
+        self.device_resize = bool(cfg.INPUT.get("DEVICE_RESIZE", False)) and is_train
         if cfg.INPUT.MASK_FORMAT != "bitmask" and cfg.MODEL.MASK_ON and is_train:
             logger.warning("INPUT.MASK_FORMAT '%s': masks are rasterised to bitmasks on the loader side either way", cfg.INPUT.MASK_FORMAT)
+
+    @staticmethod
+    def _deferred_image(image, augs):
+        """INPUT.DEVICE_RESIZE: the transforms are drawn exactly as in __call__ -- every get_transform sees an array-like of the shape the
+        image would have at that point, and reads nothing else -- but no apply_image runs.  -> (DeviceResizeImage: the decoded source, the
+        scaled size, the crop window, the flip and the window's coefficient tables; the transforms)."""
+        from .resize_tables import ResizeJob
+
+        class Shaped:
+            def __init__(self, shape):
+                self.shape = tuple(shape)
+        transforms, cur, crop, flip = [], Shaped(image.shape), None, False
+        for aug in augs:
+            t = aug.get_transform(cur)
+            if isinstance(t, EfficientDetResizeCropTransform) and crop is None and not flip:
+                crop = t
+                cur = Shaped((min(t.scaled_h, t.offset_y + t.target_size[0]) - t.offset_y,
+                              min(t.scaled_w, t.offset_x + t.target_size[1]) - t.offset_x, image.shape[2]))
+            elif isinstance(t, HFlipTransform):
+                flip = not flip
+            elif not isinstance(t, NoOpTransform):
+                raise NotImplementedError("INPUT.DEVICE_RESIZE: the transform %s is not built for the device; one EfficientDetResizeCrop "
+                                          "followed by RandomFlip is" % type(t).__name__)
+            transforms.append(t)
+        if crop is None:
+            raise NotImplementedError("INPUT.DEVICE_RESIZE needs an EfficientDetResizeCrop among the augmentations")
+        job = ResizeJob(image, (crop.scaled_h, crop.scaled_w), (crop.offset_y, crop.offset_x), cur.shape[:2], flip=flip)
+        return DeviceResizeImage(job), transforms
 
     def __call__(self, dataset_dict):
         d = copy.deepcopy(dataset_dict)
@@ -482,12 +512,16 @@ class DatasetMapper:
         d.setdefault("height", image.shape[0])
         transforms = []
         augs = self.augmentations if self.dataset_augs is None else self.dataset_augs[d["dataset_source"]]
-        for aug in augs:
-            t = aug.get_transform(image)
-            image = t.apply_image(image)
-            transforms.append(t)
-        image_shape = image.shape[:2]
-        d["image"] = torch.as_tensor(np.ascontiguousarray(image.transpose(2, 0, 1)))
+        if self.device_resize:
+            d["image"], transforms = self._deferred_image(image, augs)
+            image_shape = d["image"].shape[-2:]
+        else:
+            for aug in augs:
+                t = aug.get_transform(image)
+                image = t.apply_image(image)
+                transforms.append(t)
+            image_shape = image.shape[:2]
+            d["image"] = torch.as_tensor(np.ascontiguousarray(image.transpose(2, 0, 1)))
         if not self.is_train:
             return d
         if "annotations" in d:
@@ -538,6 +572,9 @@ class CopyPasteMapper:
         self.device_raster = bool(cfg.INPUT.get("DEVICE_RASTER", False))
         if self.device_raster:
             self._check_device_raster(cfg)
+        self.device_resize = bool(cfg.INPUT.get("DEVICE_RESIZE", False))
+        if self.device_resize:
+            self._check_device_resize(cfg)
         if self.self_prob is not None:
             self._check_self_copy(cfg)
         if self.src_modes:
@@ -551,6 +588,7 @@ class CopyPasteMapper:
             if cfg.INPUT.INST_POOL_SAMPLE_TYPE != "cas_random" or cfg.INPUT.INST_POOL_FORMAT != "RGBA":
                 raise NotImplementedError("only INST_POOL_FORMAT 'RGBA' with INST_POOL_SAMPLE_TYPE 'cas_random' is built")
             self.inst_pool = InstPool.from_config(cfg)
+            self.inst_pool.device_resize = self.device_resize
 
         # BSGAL (BS/bsgal/data/custom_build_copypaste_mapper.py:237-297, :916-930, :958-963, :1038-1057): keep the un-pasted
         # sample and add a held-out image that shows one of the pasted classes
@@ -620,6 +658,18 @@ class CopyPasteMapper:
         if bool(inp.get("ACTIVE_SELECT", False)):
             raise NotImplementedError("INPUT.DEVICE_RASTER with INPUT.ACTIVE_SELECT: BSGAL's origin / held-out samples are built on dense "
                                       "host masks")
+
+    @staticmethod
+    def _check_device_resize(cfg):
+        """This build's key INPUT.DEVICE_RESIZE is built for USE_COPY_METHOD 'none' and 'syn_copy' (with or without INPUT.DEVICE_RASTER,
+        RM_BG_PROB under INPUT.SCP_SRC_MODES, WITH_IMAGE_LABELS, USE_DIFF_BS_SIZE): there the pixels are first read on the device.  The
+        self-copy methods crop the source image's pixels in the WORKER (_call_self_copy), and BSGAL's held-out image stays on the host."""
+        inp = cfg.INPUT
+        if CopyPasteMapper._parse_method(inp.USE_COPY_METHOD) is not None:
+            raise NotImplementedError("INPUT.DEVICE_RESIZE with INPUT.USE_COPY_METHOD '{}': the self-copy methods read the source image's "
+                                      "pixels in the loader worker; 'none' and 'syn_copy' are built".format(inp.USE_COPY_METHOD))
+        if bool(inp.get("ACTIVE_SELECT", False)):
+            raise NotImplementedError("INPUT.DEVICE_RESIZE with INPUT.ACTIVE_SELECT: BSGAL's held-out image is mapped and kept on the host")
 
     @staticmethod
     def _pastes_all(inp):
@@ -860,10 +910,13 @@ class CopyPasteMapper:
         """What the TRAINING PROCESS runs on one worker result, on the current stream: upload (asynchronous from pinned memory) and
         the compositor kernel; with INPUT.ACTIVE_SELECT the un-pasted sample stays available as origin_* (it is the uploaded
         input: the compositor writes a copy)."""
-        from .copypaste import InstPool, fill_device_masks
+        from .copypaste import InstPool, fill_device_masks, materialize_resizes
         dev = torch.device(device)
         own = "blob" in result                       # the sample's tensors come out of a device copy made here
         result = unpack_sample(result, dev, self.ring)
+        if isinstance(result.get("image"), DeviceResizeImage):
+            result = materialize_resizes(result, dev)    # INPUT.DEVICE_RESIZE: first, on every exit; the image is this call's own tensor
+            own = True
         if "instances" not in result:
             result["image"] = result["image"].to(dev, non_blocking=True)
             return result
@@ -912,7 +965,9 @@ def pack_sample(d):
     sample, the three of paste_pack when it has one, the four of the self-copy source (scp_src) when it has one -- four per group
     when scp_src is a list of source groups, counted by blob_scp_n; a sample without scp_src, and one with a single source, pack
     exactly as they always did.  INPUT.DEVICE_RASTER: the instances' gt_masks is a PolygonCrossings, and the sections poly_pos (int32),
-    poly_off and inst_off (int64) stand where gt_masks would."""
+    poly_off and inst_off (int64) stand where gt_masks would.  INPUT.DEVICE_RESIZE: the image is a DeviceResizeImage, and the sections
+    rs_src (uint8), rs_jobs (int32 (J, 13)) and rs_tab (int32) stand where image would; `flat` keeps the ranges of the patches left to
+    the device unwritten."""
     if ("paste_pack" not in d and "scp_src" not in d) or "instances" not in d or not d["instances"].has("gt_masks"):
         return d
     fields = _BLOB_FIELDS if "paste_pack" in d else _BLOB_FIELDS[:4]
@@ -920,6 +975,13 @@ def pack_sample(d):
     if isinstance(gm, PolygonCrossings):      # INPUT.DEVICE_RASTER: three small sections in place of gt_masks
         fields = fields[:1] + tuple((name, lambda d, a=a: torch.from_numpy(a)) for name, a in
                                     (("poly_pos", gm.pos), ("poly_off", gm.poly_off), ("inst_off", gm.inst_off))) + fields[2:]
+    if isinstance(d["image"], DeviceResizeImage):
+        # INPUT.DEVICE_RESIZE: the sources (the image's, then those of the pool patches left to the device), the job table and the
+        # coefficient tables of the sample's ONE resize launch stand where the image would
+        from .resize_tables import assemble_jobs
+        left = d["paste_pack"].get("resize", ()) if "paste_pack" in d else ()
+        rs = assemble_jobs([d["image"].job] + [job for job, _ in left], [0] + [off for _, off in left])
+        fields = tuple((name, lambda d, a=a: torch.from_numpy(a)) for name, a in zip(("rs_src", "rs_jobs", "rs_tab"), rs)) + fields[1:]
     multi = isinstance(d.get("scp_src"), list)
     groups = []
     if multi:
@@ -986,16 +1048,22 @@ def unpack_sample(d, device, ring=None):
         n = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
         f[name] = blob[off:off + n].view(dtype).view(shape)
     out = {k: v for k, v in d.items() if not k.startswith("blob")}
-    out["image"] = f["image"]
-    if "poly_pos" in f:
-        # INPUT.DEVICE_RASTER: the offsets are validated on the host before a kernel indexes with them -- read from the host side of the
-        # blob (a copy: the slot is rewritten later), while the kernel reads the sections of the device copy
-        sec = {name: (dt, shape, off) for name, dt, shape, off in d["blob_layout"]}
+    # INPUT.DEVICE_RASTER / DEVICE_RESIZE: offsets and tables are validated on the host before a kernel indexes with them -- read from
+    # the host side of the blob (a copy: the slot is rewritten later), while the kernel reads the sections of the device copy
+    sec = {name: (dt, shape, off) for name, dt, shape, off in d["blob_layout"]}
 
-        def on_host(name):
-            dt, shape, off = sec[name]
-            a = np.dtype(dt)
-            return host[off:off + int(np.prod(shape)) * a.itemsize].numpy().view(a).copy()
+    def on_host(name):
+        dt, shape, off = sec[name]
+        a = np.dtype(dt)
+        return host[off:off + int(np.prod(shape)) * a.itemsize].numpy().view(a).copy().reshape(shape)
+    if "rs_src" in f:
+        jobs_host = on_host("rs_jobs")               # job 0 is the image: word 3 is its channel count
+        out["image"] = DeviceResizeImage(shape=(int(jobs_host[0, 3]),) + tuple(d["blob_hw"]),
+                                         pending={"src": f["rs_src"], "jobs": f["rs_jobs"], "tab": f["rs_tab"],
+                                                  "jobs_host": jobs_host, "tab_host": on_host("rs_tab")})
+    else:
+        out["image"] = f["image"]
+    if "poly_pos" in f:
         masks = PolygonCrossings(on_host("poly_pos"), on_host("poly_off"), on_host("inst_off"), tuple(d["blob_hw"]),
                                  device_copy=(f["poly_pos"], f["poly_off"], f["inst_off"]))
     else:
@@ -1185,16 +1253,24 @@ class BatchAhead:
 DEVICE_RASTER_CROSSING_BYTES = 4 << 20      # ring-slot allowance for one sample's crossing lists with INPUT.DEVICE_RASTER
 
 
-def ring_slot_bytes(size, self_copy_sources=0, device_raster=False):
+DEVICE_RESIZE_TABLE_BYTES = 1 << 20         # ring-slot allowance for one sample's resize job table and coefficient tables with INPUT.DEVICE_RESIZE
+
+
+def ring_slot_bytes(size, self_copy_sources=0, device_raster=False, device_resize=False):
     """Bytes of one SlotRing slot at TRAIN_SIZE `size`: 48 planes (the image and ~45 dense masks), 48 more per self-copy source, and
     8 MB for the rest of the blob.  INPUT.DEVICE_RASTER: no mask planes travel -- the 3 image planes, the same 8 MB, and
     DEVICE_RASTER_CROSSING_BYTES for the crossing lists and their offsets (4 bytes per crossing: room for a million, where 12 polygons
     of 120 vertices across 800 px make 70 000) -- never more than the slot without the key, which a small TRAIN_SIZE would otherwise
-    fall below; a sample beyond its slot takes the ordinary way, as any blob larger than its slot does."""
+    fall below; a sample beyond its slot takes the ordinary way, as any blob larger than its slot does.  INPUT.DEVICE_RESIZE: the
+    decoded source travels in place of the image; it can be larger than TRAIN_SIZE^2 (a downscale), so the 3 planes stay as its
+    allowance, and DEVICE_RESIZE_TABLE_BYTES is added for the tables (4 bytes x (2 + ksize) per window row and column: 2 x 1024 x 5
+    words = 40 KB for an upscale to 1024^2, 2 x 100 x 23 for a 10x downscale, a few KB per pool patch) -- again never more than the
+    slot without the keys; the patch sources (at most DEVICE_RESIZE_MAX_SRC_RATIO x `flat`) fall under the 8 MB."""
     dense = size * size * (48 + 48 * int(self_copy_sources)) + (8 << 20)
-    if device_raster:
-        return min(dense, size * size * 3 + (8 << 20) + DEVICE_RASTER_CROSSING_BYTES)
-    return dense
+    slot = min(dense, size * size * 3 + (8 << 20) + DEVICE_RASTER_CROSSING_BYTES) if device_raster else dense
+    if device_resize:
+        slot = min(dense, slot + DEVICE_RESIZE_TABLE_BYTES)
+    return slot
 DEV = {"pin": "ring", "strategy": None, "main_threads": 4}      # pin: "ring" (SlotRing) | "loader" (the DataLoader's pin thread) | "none"
 
 
@@ -1231,6 +1307,9 @@ def build_detection_train_loader(cfg, per_gpu, device, seed):
     if mapper.device_raster and torch.device(device).type != "cuda":
         raise NotImplementedError("INPUT.DEVICE_RASTER with device '{}': the masks are filled by dgx_polygons_to_bitmask on the GPU; "
                                   "there is no host fill behind the key".format(device))
+    if mapper.device_resize and torch.device(device).type != "cuda":
+        raise NotImplementedError("INPUT.DEVICE_RESIZE with device '{}': the image is resized by dgx_resize_bilinear_u8 on the GPU; "
+                                  "there is no host resize behind the key".format(device))
     mapper.set_dataset(dicts)
     rank_seed = seed * 1009 + comm.get_rank() * 131
     nw = cfg.DATALOADER.NUM_WORKERS
@@ -1245,7 +1324,8 @@ def build_detection_train_loader(cfg, per_gpu, device, seed):
         # with a self-copy method the sample also carries the source image (3 planes) and up to 99 selected source masks, each at most
         # TRAIN_SIZE^2: room for ~45 more planes (the mean of the draw over a 90-object image); beyond that, the ordinary way again
         # (INPUT.SCP_NUM_SRC sources: that many times the source's share)
-        slot = ring_slot_bytes(int(cfg.INPUT.TRAIN_SIZE), 0 if mapper.self_prob is None else int(mapper.num_src), mapper.device_raster)
+        slot = ring_slot_bytes(int(cfg.INPUT.TRAIN_SIZE), 0 if mapper.self_prob is None else int(mapper.num_src), mapper.device_raster,
+                               mapper.device_resize)
         try:
             ring = SlotRing(nw, (int(cfg.DATALOADER.PREFETCH_FACTOR) + 2) * per_gpu, slot)
         except Exception as e:

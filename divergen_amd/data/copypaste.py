@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from ..layers.copy_paste import BLEND_MODES, BLEND_MODES_ALL, PackedPastes, copy_paste
-from ..structures import BitMasks, Boxes, Instances, PolygonCrossings
+from ..structures import BitMasks, Boxes, DeviceResizeImage, DeviceResizePatch, Instances, PolygonCrossings
 
 
 def check_cp_method(cp_method, allow_poisson=False):
@@ -74,6 +74,49 @@ def fill_device_masks(data, device):
     return dict(data, instances=filled)
 
 
+# INPUT.DEVICE_RESIZE: a pool patch keeps its source crop (and is resized on the device) when the source has at most this many times the
+# pixels of the resized patch; a larger source is resized by the worker, as without the key.  The factor bounds what the patch sources
+# add to the sample blob: at most 4 x the bytes of `flat`, inside the ring slot's 8 MB for "the rest".
+DEVICE_RESIZE_MAX_SRC_RATIO = 4
+
+
+def materialize_resizes(data, device):
+    """INPUT.DEVICE_RESIZE, training-process half: a sample whose image is a DeviceResizeImage gets its (3, ch, cw) uint8 tensor here,
+    and the pool patches that were left to the device their bytes in `flat` -- ONE dgx_resize_bilinear_u8 launch on the CURRENT stream
+    (the loader's side stream), in front of the mask fill, dgx_remove_background and the compositor.  From here on the sample is byte for
+    byte what the key-off path carries.  Any other sample is returned as it is."""
+    img = data.get("image")
+    if not isinstance(img, DeviceResizeImage):
+        return data
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("INPUT.DEVICE_RESIZE needs the GPU kernel (dgx_resize_bilinear_u8); device is %s" % device)
+    from ..layers.resize_ops import resize_bilinear_u8
+    from .resize_tables import assemble_jobs
+    data = dict(data)
+    pk = data.get("paste_pack")
+    if img.pending is not None:                      # out of the blob: everything is on the device already, `flat` included
+        p = img.pending
+        src, jobs_host, tab_host, jobs_dev, tab_dev = p["src"], p["jobs_host"], p["tab_host"], p["jobs"], p["tab"]
+        flat = pk["flat"] if pk is not None else None
+    else:                                            # a sample that crossed unpacked (or never left this process)
+        jobs, offs = [img.job], [0]
+        flat = None
+        if pk is not None:
+            pk = data["paste_pack"] = dict(pk)
+            for job, off in pk.pop("resize", ()):
+                jobs.append(job)
+                offs.append(off)
+            if len(jobs) > 1:
+                flat = pk["flat"] = pk["flat"].to(dev, non_blocking=True)
+        src, jobs_host, tab_host = assemble_jobs(jobs, offs)
+        src, jobs_dev, tab_dev = torch.from_numpy(src).to(dev, non_blocking=True), None, None
+    out = torch.empty(img.shape, dtype=torch.uint8, device=dev)
+    resize_bilinear_u8(src, jobs_host, tab_host, image=out, flat=flat, jobs_dev=jobs_dev, tab_dev=tab_dev)
+    data["image"] = out
+    return data
+
+
 def largest_connected_component(mask):
     """Role of get_largest_connect_component (mapper.py:25-36, cv2 contours): keep the largest blob."""
     from scipy import ndimage
@@ -108,6 +151,7 @@ class InstPool:
         self.loader = loader or self._pil_loader
         self.allow_poisson = bool(allow_poisson)
         self.cp_method = check_cp_method(cp_method, self.allow_poisson)
+        self.device_resize = False        # INPUT.DEVICE_RESIZE (set by CopyPasteMapper): patches may leave load_rgba un-resized
         self.rng = random.Random()        # blend-mode draws only (seed: the loader's _worker_init); never the global `random`
 
     def seed(self, seed):
@@ -200,9 +244,15 @@ class InstPool:
             tw, th = int(tw), int(th)
             if tw < 5 or tw >= W or th < 5 or th >= H:
                 return None
-        rgba = self._resize(rgba, tw, th)
+        if self.device_resize and rgba.shape[0] * rgba.shape[1] <= DEVICE_RESIZE_MAX_SRC_RATIO * th * tw:
+            rgba = DeviceResizePatch(rgba, th, tw)                                          # INPUT.DEVICE_RESIZE: resized (and flipped) on the device
+        else:
+            rgba = self._resize(rgba, tw, th)
         if np.random.rand() < 0.5:                                                          # RandomFlip(horizontal)
-            rgba = np.ascontiguousarray(rgba[:, ::-1])
+            if isinstance(rgba, DeviceResizePatch):
+                rgba.flip = True                                                            # its job mirrors the resized patch
+            else:
+                rgba = np.ascontiguousarray(rgba[:, ::-1])
         return rgba, label
 
     @staticmethod
@@ -261,6 +311,10 @@ class InstPool:
         data = dict(data)
         data["paste_pack"] = {"flat": flat, "desc": desc, "labels": labels, "modes": self.draw_modes(len(pastes)),
                               "K": len(pastes)}
+        # INPUT.DEVICE_RESIZE: one interleaved RGBA job per patch left to the device, its destination the patch's range of `flat`
+        resize = [(p[0].job(), int(d[0])) for p, d in zip(pastes, desc.tolist()) if isinstance(p[0], DeviceResizePatch)]
+        if resize:
+            data["paste_pack"]["resize"] = resize
         data["paste_labels"], data["paste_filename_list"] = [p[3] for p in pastes], names
         return data
 
@@ -269,6 +323,7 @@ class InstPool:
         """Training-process half: the prepared sample's tensors go to `device` (asynchronously when they are pinned) and ONE
         libdgx call (copy_paste) on the CURRENT stream blends all K patches, updates masks / boxes and drops covered objects.  The
         caller chooses the stream (data/build.py: a side stream, one batch ahead of the training stream)."""
+        data = materialize_resizes(data, device)     # INPUT.DEVICE_RESIZE: the image and the device-resized patches, before they are read
         data = fill_device_masks(data, device)       # INPUT.DEVICE_RASTER: the ground-truth masks are filled here, before they are read
         pk = data["paste_pack"]
         inst = data["instances"]

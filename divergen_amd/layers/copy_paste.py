@@ -74,10 +74,14 @@ def _layout(pastes):
 
 def pack_pastes_host(pastes):
     """list of (rgba uint8 (h, w, 4) numpy, x0, y0, label) -> (flat uint8, desc int32 (K, 5), labels int64 (K)) as CPU tensors:
-    what a LOADER WORKER hands the training process for one image (no device, no libdgx).  K = 0 gives a 4-byte flat buffer."""
+    what a LOADER WORKER hands the training process for one image (no device, no libdgx).  K = 0 gives a 4-byte flat buffer.  A patch that
+    is still a structures.DeviceResizePatch (INPUT.DEVICE_RESIZE) gets its range of `flat` but no bytes: the resize kernel writes them."""
+    from ..structures import DeviceResizePatch
     desc, nbytes, labels = _layout(pastes)
     host = np.zeros(max(nbytes, 4), dtype=np.uint8)
     for (rgba, _, _, _), d in zip(pastes, desc.tolist()):
+        if isinstance(rgba, DeviceResizePatch):
+            continue
         n = d[1] * d[2] * 4
         a = rgba.detach().cpu().numpy() if isinstance(rgba, torch.Tensor) else np.asarray(rgba)
         host[d[0]:d[0] + n] = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)

@@ -229,6 +229,34 @@ class PolygonCrossings:
         return BitMasks(out.view(torch.bool))
 
 
+class DeviceResizeImage:
+    """What d["image"] carries before the resize (INPUT.DEVICE_RESIZE): the decoded source and the numbers of its resize-crop-flip, in
+    place of the mapped (3, ch, cw) image -- which `shape` reports, so every reader of `.shape[-2:]` works unchanged.
+      job      data/resize_tables.ResizeJob (the (h, w, 3) source, the scaled size, the crop window, the flip, both coefficient tables):
+               what a loader worker builds, and what crosses the process boundary when the sample is not packed into a blob;
+      pending  after unpack_sample, instead of job: dict(src, jobs, tab -- tensors, views of the uploaded blob -- and jobs_host,
+               tab_host, the host copies that are validated before the launch).  Job 0 is the image, the others are pool patches.
+    data/copypaste.py:materialize_resizes turns it into the uint8 tensor with ONE dgx_resize_bilinear_u8 launch."""
+
+    def __init__(self, job=None, shape=None, pending=None):
+        self.job, self.pending = job, pending
+        self.shape = tuple(int(v) for v in shape) if shape is not None else (job.channels,) + tuple(job.crop_hw)
+        self.dtype, self.is_cuda = torch.uint8, False
+
+
+class DeviceResizePatch:
+    """An instance-pool patch before its resize (INPUT.DEVICE_RESIZE): the cleaned RGBA source crop, the target size and the flip.
+    `shape` is the resized patch's (th, tw, 4): placement and the flat layout read nothing else."""
+
+    def __init__(self, src, th, tw, flip=False):
+        self.src, self.flip = np.ascontiguousarray(src, dtype=np.uint8), bool(flip)
+        self.shape = (int(th), int(tw), 4)
+
+    def job(self):
+        from ..data.resize_tables import ResizeJob
+        return ResizeJob(self.src, self.shape[:2], flip=self.flip, interleaved=True)
+
+
 def _join_field(values):
     """One field of several Instances joined along the instance axis: tensors by torch.cat, lists by concatenation, anything
     else through its own static `cat` (Boxes, BitMasks, ...)."""

@@ -481,6 +481,28 @@ int dgx_polygons_to_bitmask(const int32_t* pos, int64_t n_pos, const int64_t* po
                             const int64_t* host_poly_off, const int64_t* host_inst_off, int N, int P, int H, int W,
                             uint8_t* masks, void* stream);
 
+/* Pillow-exact 8-bit BILINEAR resize (INPUT.DEVICE_RESIZE): J independent jobs in one launch, each byte for byte
+ * `Image.resize((out_w, out_h), Image.BILINEAR)` of one interleaved 8-bit source restricted to a crop window, optionally mirrored.
+ *   src u8 (src_bytes), device: the sources, interleaved (h, w, C), C = 3 or 4; a 4-channel source starts 4-byte aligned.
+ *   jobs i32 (J, 13), given twice: the DEVICE copy the kernel reads and the HOST copy (host_jobs, the same values) validated here.
+ *       Words: src_off (bytes into src), src_h, src_w, C, ch, cw (the window), flags, dst_off (bytes into the destination), h_off,
+ *       h_ksize, v_off, v_ksize (words into tab), tile0.  flags: 1 = mirror (window column x lands at cw - 1 - x), 2 = the
+ *       destination is `flat`, interleaved (ch, cw, 4), C = 4 -- otherwise `image`, planar (C, ch, cw) --, 4 = RGBA premultiply on
+ *       load and un-premultiply on store (what Pillow does to mode "RGBA" whenever a size changes).  tile0 = number of 64 x 16
+ *       output tiles of the jobs before this one.
+ *   tab i32 (tab_words), device + host copy (host_tab): per job and axis, for the window's L = cw (ch) outputs only, `bounds` (L, 2)
+ *       = (first source index, tap count n <= ksize) followed by `k` (L, ksize): Pillow's precompute_coeffs + normalize_coeffs_8bpc
+ *       (2^22 fixed point).  One pass: clamp((2^21 + sum src * k) >> 22, 0, 255); horizontal first, rounded to bytes, then vertical.
+ *       An axis that keeps its size carries identity taps (n = 1, k = 2^22).
+ * Validated on the host copies before anything is launched: sizes >= 1, C, flags, every source range inside src, every destination
+ * range inside its buffer, every table inside tab, first + n <= the source size for every bounds row, tile0.  Every byte of every
+ * job's window is written, nothing else; no floating point, no atomics: two calls give the same bytes (jobs must not overlap).
+ * J == 0 -> DGX_OK, nothing launched.  Errors, nothing launched: a failed validation, a negative size, a NULL array that would be
+ * used -> DGX_ERR_BAD_ARG;  a buffer of 2^31 bytes / words or more -> DGX_ERR_UNSUPPORTED. */
+int dgx_resize_bilinear_u8(const uint8_t* src, int64_t src_bytes, const int32_t* jobs, const int32_t* tab, const int32_t* host_jobs,
+                           const int32_t* host_tab, int J, int64_t tab_words, uint8_t* image, int64_t image_bytes, uint8_t* flat,
+                           int64_t flat_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Fused parameter update over a flat arena: per-element gradient value clip, AdamW, EMA lerp of
  * the PRE-step weights (the reference updates the EMA before optimizer.step: DG/train_net.py:262-284),
