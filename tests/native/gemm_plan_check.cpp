@@ -4,6 +4,8 @@
 //   pin  M N K mode res_bf16 ws  form bm bn           expected under default knobs at reserved CUs 0 and 16; form -1: LW or TWO
 //   k192 M N K mode res_bf16 ws                       must take the resident-panel kernel at reserved CUs 0 and 16
 //   row  ngrp Ms.. M N K mode res_bf16 conv ws lw reserved  form bm bn splits      a recorded dispatch of the parent library
+//   tab  M N K mode res_bf16 relu ws  lw two_wg tile splitk k192  reserved  form bm bn splits      a table row of tests/_gemm_ref64.py: all
+//        five knobs as dgx_dev_set takes them (tile = bm * 1000 + bn), reserved CUs, and what dgx_gemm_last_form must report
 // Then the invariants of every plan over a grid of small shapes.  Prints "ok <cases> <plans>" and exits 0, or the first failure.
 #include "../../divergen_amd/csrc/gemm_plan.h"
 
@@ -121,6 +123,18 @@ static int run_cases(const char* path) {
             } else {
                 CHECK(q.ngrp > 0 && lw == 0 && p.form == FORM_NT, "%s -> form %d", line.c_str(), p.form);
             }
+        } else if (kind == "tab") {
+            int res_bf16, relu, tile, reserved, form, bm, bn, splits;
+            DevKnobs dev;
+            s >> q.M >> q.N >> q.K >> q.mode >> res_bf16 >> relu >> q.ws_bytes >> dev.lw >> dev.two_wg >> tile >> dev.splitk >> dev.k192 >> reserved >> form >> bm >>
+                bn >> splits;
+            CHECK(!s.fail(), "bad line: %s", line.c_str());
+            q.res_bf16 = res_bf16; q.relu = relu != 0;
+            dev.tile_bm = tile / 1000; dev.tile_bn = tile % 1000;                    // dgx_dev_set("gemm_tile")
+            const GemmPlan p = plan(q, dev, (reserved + 7) / 8 > 24 ? 24 : (reserved + 7) / 8);      // dgx_set_reserved_cus
+            const bool k = p.form == FORM_K192;
+            CHECK(p.form == form && (k ? 32 : p.bm) == bm && (k ? 192 : p.bn) == bn && (k ? 1 : p.splits) == splits,
+                  "%s -> form %d %dx%d splits %d x %d, per XCD %d", line.c_str(), p.form, k ? 32 : p.bm, k ? 192 : p.bn, k ? 1 : p.splits, p.kt_per_split, p.per_xcd);
         } else {
             CHECK(false, "bad line: %s", line.c_str());
         }
