@@ -182,6 +182,10 @@ SIGNATURES = {
     "dgx_zs_gather": (c_i, [c_p, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p]),
     "dgx_remap_labels": (c_i, [c_p, c_i64, c_p, c_i, c_p, c_p]),
     "dgx_zs_logits_f32": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_i64, c_p]),
+    "dgx_text_embed": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
+    "dgx_causal_attention_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p]),
+    "dgx_quick_gelu": (c_i, [c_p, c_p, c_i64, c_p]),
+    "dgx_text_eot_project": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p]),
     "dgx_gelu_fwd": (c_i, [c_p, c_p, c_i64, c_p]),
     "dgx_gelu_bwd_workspace_bytes": (c_i64, [c_i, c_i]),
     "dgx_gelu_bwd_colsum": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_p, c_p]),

@@ -38,3 +38,17 @@ def reset_cls_vocabularies(cfg):
         raise ResetClsTestsError("MODEL.RESET_CLS_TESTS: MODEL.TEST_CLASSIFIERS (%d) and MODEL.TEST_NUM_CLASSES (%d) need one entry per "
                                  "DATASETS.TEST set (%d)" % (len(paths), len(counts), len(names)))
     return list(zip(names, paths, counts))
+
+
+def text_vocabulary(encoder, names, prompt="a ", chunk=256):
+    """Class embeddings of a list of names from the text encoder, as BS/bsgal/predictor.py:15-23 makes a custom test vocabulary:
+    (C, embed_dim) fp32 on the host, one row per name of `prompt + name`.  Saved as .npy it is what ZEROSHOT_WEIGHT_PATH /
+    MODEL.TEST_CLASSIFIERS read; `reset_cls_test(model, emb.permute(1, 0).contiguous(), C)` takes it as a tensor (the reference's
+    own transpose).  The names run through the encoder `chunk` at a time."""
+    names = list(names)
+    if not names:
+        raise ValueError("text_vocabulary: no names")
+    rows = []
+    for i in range(0, len(names), chunk):
+        rows.append(encoder([prompt + n for n in names[i:i + chunk]]).detach().float().cpu())
+    return torch.cat(rows, 0)

@@ -1193,6 +1193,30 @@ int dgx_mask_bce(const void* logits, int64_t row_stride, int64_t inner, const ui
                  float* workspace, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * CLIP text encoder, forward only (DG/divergen/modeling/text/text_encoder.py: CLIPTEXT.encode_text, :154-163; the encoder is
+ * frozen wherever the reference uses it).  The linear layers run on dgx_gemm_bf16_nt, ln_1 / ln_2 on dgx_layernorm_fwd in token
+ * order; these are the pieces in between (csrc/text_encoder.hip).
+ *   dgx_text_embed            x f32 (B, L, W) = token_embedding[tokens[b][l]] + positional_embedding[l] (:155-156), the residual
+ *                             stream, and eot i32 (B) = the FIRST index of the row's largest token (text.argmax(dim=-1), :162).
+ *                             tokens_host (host) is the same (B, L) i64 array in host memory: a token outside [0, vocab) there is
+ *                             DGX_ERR_BAD_ARG and nothing is launched; the kernel reads `tokens` (device) and never reads outside
+ *                             the table whatever that holds (such a row becomes zeros).
+ *   dgx_causal_attention_fwd  qkv bf16 (B, L, 3, nH, 64): nn.MultiheadAttention's in_proj output (q | k | v, each split into heads),
+ *                             batch-major rows -> out bf16 (B, L, nH * 64) = softmax(q k^T / 8 + causal mask) v per head, the input
+ *                             of out_proj.  1 <= L <= DGX_TEXT_MAX_L, DGX_ERR_BAD_ARG (nothing launched) otherwise.  Row l is a
+ *                             function of rows 0..l only.  bf16 P feeds the MFMA; fp32 logits, statistics and sums.
+ *   dgx_quick_gelu            y = x * sigmoid(1.702 x) (:26-28), x / y bf16 (n), fp32 arithmetic; y may alias x.
+ *   dgx_text_eot_project      out f32 (B, E) = ln_final(x[b, eot[b]]) @ text_projection (W, E), all fp32 (:160-162); eot outside
+ *                             [0, L) is clamped.  W <= 12288. */
+#define DGX_TEXT_MAX_L 96
+int dgx_text_embed(const int64_t* tokens_host, const int64_t* tokens, const float* token_embedding, const float* positional_embedding,
+                   int B, int L, int W, int vocab, float* x, int32_t* eot, void* stream);
+int dgx_causal_attention_fwd(const void* qkv, void* out, int B, int L, int nH, void* stream);
+int dgx_quick_gelu(const void* x, void* y, int64_t n, void* stream);
+int dgx_text_eot_project(const float* x, const int32_t* eot, const float* ln_weight, const float* ln_bias, const float* projection,
+                         int B, int L, int W, int E, float eps, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Launch accounting for measurement (bench.py's `roofline` objects; no reference counterpart -- the reference has no
  * device-side instrumentation).  After dgx_prof_enable(1) the entry points of a family bracket each call with HIP events
  * on the stream they launch on and add the call's algorithmic FLOP and bytes (operands read once, results written once)
