@@ -2,7 +2,10 @@
 // (CN/modeling/dense_heads/centernet_head.py:52-75: Conv3x3 -> GroupNorm(32, 256) -> ReLU, x4 per level).
 // x (N, HW, C) bf16, 8 channels per group (C = 8 G): one 16-byte vector = one group at one pixel, so every
 // pass is a fully coalesced stream.  HBM-bound: forward reads x twice + writes y once; backward reads x, dy twice.
-//   stats   : slab partial sums per (n, g) in fp32 (shifted sums: no cancellation)
+//   stats   : slab partial sums per (n, g) in fp32, of x - x0 with x0 the group's first element: var = E[d^2] - E[d]^2 is free of
+//             cancellation only while x0 lies near the group mean -- its relative error grows like 1 + (x0 - mean)^2 / var times the
+//             summation error, below the bf16 rounding of y up to |x0 - mean| = 8 sigma and above it at 300 sigma over 16400 pixels
+//             (tests/test_host_norm_ref.py::test_x0_cancellation_against_the_bf16_rounding quantifies both)
 //   apply   : folds the partials into mean / rstd per workgroup, then y = relu?((x - mean) * rstd * gamma + beta)
 //   bwd red : per (n, g): s1 = sum dyh*gamma, s2 = sum dyh*gamma*xhat and the per-channel sums for dgamma / dbeta
 //   bwd dx  : dx = rstd * (dyh*gamma - (s1 + xhat*s2)/m),  dyh = dy * (y > 0)
@@ -20,7 +23,8 @@ __device__ __forceinline__ float block_sum(float v, float* red) {   // 256 threa
 }  // namespace
 
 // grid (N*G, S): slab s of the pixels of one (n, g).  Sums are taken of x - x0 (x0 = the group's first element) so that
-// var = E[d^2] - E[d]^2 does not cancel when the mean is large against the spread.  part[(ng*S + s)*2 + {0,1}].
+// var = E[d^2] - E[d]^2 does not cancel when the mean is large against the spread -- as long as x0 itself is near the mean (see the
+// header: an outlying first element brings the cancellation back).  part[(ng*S + s)*2 + {0,1}].
 __device__ __forceinline__ void gn_stats_partial_body(const uint16_t* __restrict__ x, float* __restrict__ part, int HW, int C,
                                                                int G, int S, int bx, int by) {
     __shared__ float red[4];
@@ -379,8 +383,8 @@ extern "C" int dgx_groupnorm_fwd(const void* x, const float* gamma, const float*
     hipStream_t st = (hipStream_t)stream;
     const int S = gn_slabs(N * G, HW, G);
     if (!scratch) return DGX_ERR_BAD_ARG;
+    if (G > 256) return DGX_ERR_UNSUPPORTED;       // mu_s / rs_s of the apply kernel hold 256 groups; refused before anything is launched
     hipLaunchKernelGGL(gn_stats_partial_kernel, G == GN_RG ? dim3(S, N) : dim3(N * G, S), dim3(256), 0, st, (const uint16_t*)x, scratch, HW, C, G, S);
-    if (G > 256) return DGX_ERR_UNSUPPORTED;
     const int64_t per_n = (int64_t)HW * G;
     int bpn = (int)((per_n + 255) / 256);
     const int cap = (4096 + N - 1) / N;
@@ -398,10 +402,10 @@ extern "C" int dgx_groupnorm_bwd(const void* x, const void* dy, const float* mea
     if (!x || !dy || !mean || !rstd || !gamma || !beta || !dx || !dgamma || !dbeta || !part || C != 8 * G) return DGX_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int S = gn_slabs(N * G, HW, G);
+    if (G > 256) return DGX_ERR_UNSUPPORTED;       // s1_s / s2_s of the dx kernel hold 256 groups; refused before anything is launched
     float* part2 = part + (int64_t)N * G * 18;      // scratch layout: [N*G][18] folded, then [N*G][S][18]
     hipLaunchKernelGGL(gn_bwd_reduce_kernel, G == GN_RG ? dim3(S, N) : dim3(N * G, S), dim3(256), 0, st, (const uint16_t*)x, (const uint16_t*)dy, mean, rstd, gamma,
                        beta, part2, HW, C, G, relu, S);
-    if (G > 256) return DGX_ERR_UNSUPPORTED;
     const int64_t per_n = (int64_t)HW * G;
     int bpn = (int)((per_n + 255) / 256);
     const int cap = (4096 + N - 1) / N;
