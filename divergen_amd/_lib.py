@@ -160,6 +160,10 @@ SIGNATURES = {
     "dgx_wsddn_workspace_floats": (c_i64, [c_i, c_i, c_i]),
     "dgx_wsddn_loss": (c_i, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_i64,
                              c_p, c_i64, c_p, c_i, c_p]),
+    "dgx_caption_prepare": (c_i, [c_p, c_i64, c_i, c_i, c_i, c_p, c_p]),
+    "dgx_caption_workspace_floats": (c_i64, [c_i, c_i]),
+    "dgx_caption_loss": (c_i, [c_p, c_i64, c_i64, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_f, c_i, c_p, c_f, c_f, c_f, c_p, c_p, c_p, c_p,
+                               c_p, c_i64, c_p, c_i, c_p]),
     "dgx_paste_masks": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p]),
     "dgx_paste_rle": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
     "dgx_rle_encode": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),

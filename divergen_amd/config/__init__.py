@@ -196,6 +196,16 @@ def get_cfg():
     #   (dgx_dyn_class_sample, dgx_zs_gather, dgx_remap_labels, dgx_zs_logits_f32; divergen_amd/csrc/dyn_vocab.hip, config/dynamic_vocab.py).  Without the
     #   key DYNAMIC_CLASSIFIER is refused at start-up.
     cfg.MODEL.DYNAMIC_VOCAB = False
+    #   MODEL.CAPTION_TRAIN: admits MODEL.WITH_CAPTION True (the model owns the frozen CLIP text encoder and trains the open-vocabulary
+    #   classifier on image captions), DATALOADER.DATASET_ANN 'caption' / 'captiontag', MODEL.SYNC_CAPTION_BATCH with
+    #   MODEL.CAP_BATCH_RATIO (the caption rows of all ranks gathered on every step) and makes MODEL.ROI_BOX_HEAD.CAPTION_WEIGHT /
+    #   NEG_CAP_WEIGHT take effect: dgx_caption_prepare, dgx_caption_loss (divergen_amd/csrc/caption_loss.hip, config/caption.py).
+    #   Without the key all of these are refused at start-up, as before.
+    #   MODEL.TEXT_ENCODER_WEIGHTS / MODEL.TEXT_ENCODER_BPE: the paths of clip's text state dict and BPE merges file (this build never
+    #   downloads); the encoder's geometry is read from the state dict's shapes.
+    cfg.MODEL.CAPTION_TRAIN = False
+    cfg.MODEL.TEXT_ENCODER_WEIGHTS = ""
+    cfg.MODEL.TEXT_ENCODER_BPE = ""
     #   SOLVER.ALLREDUCE_DTYPE: "fp32" (the reference's DDP: gradients all-reduced as they are) or "bf16" (gradient buckets go over
     #   xGMI as bf16, half the bytes per step; engine/ddp.py ArenaReducer(wire_dtype=...)).
     cfg.SOLVER.ALLREDUCE_DTYPE = "fp32"

@@ -36,7 +36,10 @@ def check_filter_empty(filter_empty, dataset_ann):
 
 
 def check_model_keys(cfg):
-    """The model side; a configuration without WITH_IMAGE_LABELS passes untouched."""
+    """The model side; a configuration without WITH_IMAGE_LABELS passes untouched (behind MODEL.CAPTION_TRAIN, config/caption.py
+    first demands what MODEL.WITH_CAPTION needs -- WITH_IMAGE_LABELS among it)."""
+    from .caption import check_model_keys as check_caption_keys, with_caption
+    check_caption_keys(cfg)
     if not cfg.WITH_IMAGE_LABELS:
         return
     h = cfg.MODEL.ROI_BOX_HEAD
@@ -45,7 +48,7 @@ def check_model_keys(cfg):
     if h.WITH_SOFTMAX_PROP and not ws_prop:
         _refuse("MODEL.ROI_BOX_HEAD.WITH_SOFTMAX_PROP", "the proposal-score branch is admitted by MODEL.ROI_BOX_HEAD.WS_PROP_SCORE True only")
     for key, on in (("MODEL.ROI_BOX_HEAD.SOFTMAX_WEAK_LOSS", h.SOFTMAX_WEAK_LOSS),
-                    ("MODEL.ROI_BOX_HEAD.ADD_FEATURE_TO_PROP", h.ADD_FEATURE_TO_PROP), ("MODEL.WITH_CAPTION", cfg.MODEL.WITH_CAPTION),
+                    ("MODEL.ROI_BOX_HEAD.ADD_FEATURE_TO_PROP", h.ADD_FEATURE_TO_PROP), ("MODEL.WITH_CAPTION", cfg.MODEL.WITH_CAPTION and not with_caption(cfg)),
                     ("MODEL.DYNAMIC_CLASSIFIER", cfg.MODEL.DYNAMIC_CLASSIFIER and not cfg.MODEL.get("DYNAMIC_VOCAB", False))):
         if on:
             _refuse(key, "not built: image-label co-training covers the five row-selection losses and, with MODEL.ROI_BOX_HEAD.WS_PROP_SCORE, "
@@ -73,12 +76,17 @@ def check_loader_keys(cfg, per_gpu):
     for key in ("DATASET_ANN", "DATASET_RATIO", "USE_RFS") + (("DATASET_BS", "DATASET_INPUT_SIZE", "DATASET_INPUT_SCALE") if d.USE_DIFF_BS_SIZE else ()):
         if len(d[key]) < n:
             raise ValueError("DATALOADER.%s has %d entries for %d DATASETS.TRAIN" % (key, len(d[key]), n))
-    for a in list(d.DATASET_ANN)[:n]:
-        if a not in ANN_TYPES:
-            _refuse("DATALOADER.DATASET_ANN %r" % (a,), "one of %s (caption / prop / proptag annotation types are not built)" % (ANN_TYPES,))
-    if any(a == "image" for a in list(d.DATASET_ANN)[:n]):
+    from .caption import admitted_ann_types, check_loader_keys as check_caption_loader
+    anns = list(d.DATASET_ANN)[:n]
+    check_caption_loader(cfg, anns, [int(b) for b in list(d.DATASET_BS)[:n]] if d.USE_DIFF_BS_SIZE else [int(per_gpu)] * n)
+    admitted = admitted_ann_types(cfg, ANN_TYPES)
+    for a in anns:
+        if a not in admitted:
+            _refuse("DATALOADER.DATASET_ANN %r" % (a,), "one of %s (caption / prop / proptag annotation types are not built)" % (admitted,))
+    if any(a != "box" for a in anns):
         if not cfg.WITH_IMAGE_LABELS:
-            raise ValueError("DATALOADER.DATASET_ANN holds 'image' but WITH_IMAGE_LABELS is False: the model would refuse the batch")
+            raise ValueError("DATALOADER.DATASET_ANN holds %s but WITH_IMAGE_LABELS is False: the model would refuse the batch"
+                             % ", ".join(sorted(set(repr(a) for a in anns if a != "box"))))
         check_filter_empty(d.FILTER_EMPTY_ANNOTATIONS, list(d.DATASET_ANN)[:n])
     if cfg.WITH_IMAGE_LABELS and not multi:
         raise ValueError("WITH_IMAGE_LABELS needs DATALOADER.SAMPLER_TRAIN 'MultiDatasetSampler' (got %r): a batch must hold one "

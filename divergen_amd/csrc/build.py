@@ -16,7 +16,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["window_attention.hip", "window_shuffle.hip", "roi_align.hip", "nms_boxes.hip",
-           "centernet_targets.hip", "compositor.hip", "poisson_blend.hip", "self_copy.hip", "remove_background.hip", "polygon_raster.hip", "resize_u8.hip", "optim.hip", "im2col.hip", "wgrad256.hip", "gemm_nt.hip", "gemm_lw.hip", "gemm_k192.hip", "wgrad_lw.hip", "transpose.hip", "prof.hip", "preprocess.hip", "mask_loss.hip", "layernorm.hip", "l2norm.hip", "residual.hip", "colsum.hip", "groupnorm.hip", "gelu.hip", "detic_loss.hip", "dyn_vocab.hip", "text_encoder.hip", "centernet_loss.hip", "cascade_refine.hip", "image_label.hip", "wsddn_loss.hip", "mask_paste.hip", "lvis_eval.hip", "grad_bank.hip", "roi_sample.hip", "centernet_decode.hip", "topk_sort.hip", "resnet_ops.hip", "abi.hip"]
+           "centernet_targets.hip", "compositor.hip", "poisson_blend.hip", "self_copy.hip", "remove_background.hip", "polygon_raster.hip", "resize_u8.hip", "optim.hip", "im2col.hip", "wgrad256.hip", "gemm_nt.hip", "gemm_lw.hip", "gemm_k192.hip", "wgrad_lw.hip", "transpose.hip", "prof.hip", "preprocess.hip", "mask_loss.hip", "layernorm.hip", "l2norm.hip", "residual.hip", "colsum.hip", "groupnorm.hip", "gelu.hip", "detic_loss.hip", "dyn_vocab.hip", "text_encoder.hip", "centernet_loss.hip", "cascade_refine.hip", "image_label.hip", "wsddn_loss.hip", "caption_loss.hip", "mask_paste.hip", "lvis_eval.hip", "grad_bank.hip", "roi_sample.hip", "centernet_decode.hip", "topk_sort.hip", "resnet_ops.hip", "abi.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-munsafe-fp-atomics", "-Wno-unused-result"]

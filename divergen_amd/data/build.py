@@ -94,6 +94,8 @@ def load_lvis_json(json_file, image_root):
         rec["neg_category_ids"] = [catid2contid[x] for x in img.get("neg_category_ids", [])]
         if "pos_category_ids" in img:
             rec["pos_category_ids"] = [catid2contid[x] for x in img["pos_category_ids"]]
+        if "captions" in img:               # lvis_v1.py:91-92: the captions of a caption-supervised image ride on the record
+            rec["captions"] = img["captions"]
         image_id = rec["image_id"] = img["id"]
         objs = []
         for anno in img_ann.get(image_id, []):

@@ -90,15 +90,21 @@ def write_mini_lvis(root, n_images=32, image_hw=(480, 640), n_obj=12, n_pool=64,
     return {"root": root, "pool_json": os.path.join(root, "pool.json"), "n_images": n_images, "n_pool": n_pool}
 
 
-def write_mini_image_labels(root, split="imagenet_lvis_mini", n_images=8, image_hw=(120, 160), n_cats=1203, seed=0):
+CAPTION_WORDS = ("low", "lower", "newer", "a", "new", "row", "of", "lows")      # the test merges file (l o / lo w</w> / e r</w> / n e / ne w / new er</w>) tokenizes these
+
+
+def write_mini_image_labels(root, split="imagenet_lvis_mini", n_images=8, image_hw=(120, 160), n_cats=1203, seed=0, captions=False):
     """A small IMAGE-LABELLED source in the ImageNet-LVIS json format (WITH_IMAGE_LABELS): `root`/imagenet/<split>/*.jpg and
     `root`/imagenet/<split>.json whose images carry `pos_category_ids` (1-based LVIS category ids, one to three per image) and no
-    annotations; every second image is portrait.  Returns dict(json, image_root, n_images); register it with
+    annotations; every second image is portrait.  captions: every image also carries `captions`, one to three strings of three to
+    eight CAPTION_WORDS each (MODEL.WITH_CAPTION; drawn from a generator of their own, the rest of the split is unchanged).
+    Returns dict(json, image_root, n_images); register it with
     data.build.register_lvis_instances(name, json, image_root).  Deterministic in `seed`."""
     import json
     import os
     from PIL import Image
     rng = np.random.default_rng(seed)
+    cap_rng = np.random.default_rng([seed, 0xCA9])
     image_root = os.path.join(root, "imagenet", split)
     os.makedirs(image_root, exist_ok=True)
     H, W = image_hw
@@ -109,6 +115,9 @@ def write_mini_image_labels(root, split="imagenet_lvis_mini", n_images=8, image_
         Image.fromarray(low).resize((w, h), Image.BICUBIC).save(os.path.join(image_root, "%08d.jpg" % (i + 1)), quality=90)
         pos = sorted(set(int(c) for c in rng.integers(1, n_cats + 1, int(rng.integers(1, 4)))))
         images.append({"id": i + 1, "height": h, "width": w, "file_name": "%08d.jpg" % (i + 1), "pos_category_ids": pos})
+        if captions:
+            images[-1]["captions"] = [" ".join(CAPTION_WORDS[int(k)] for k in cap_rng.integers(0, len(CAPTION_WORDS), int(cap_rng.integers(3, 9))))
+                                      for _ in range(int(cap_rng.integers(1, 4)))]
     cats = [{"id": c, "name": "c%d" % c} for c in range(1, n_cats + 1)]
     path = os.path.join(root, "imagenet", split + ".json")
     with open(path, "w") as f:

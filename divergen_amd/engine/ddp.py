@@ -68,7 +68,7 @@ class ArenaReducer:
         self._learned = {}             # segment-mode combination -> learned signal counts
         self._expected = None          # this step's counts; None = calibrating (no early launches)
         self._mode_key = None          # taken at the step's first signal (every segment has run its forward by then)
-        self.step_kind = None          # the step's annotation type ('box' | 'image'), set by a WITH_IMAGE_LABELS trainer before backward
+        self.step_kind = None          # the step's annotation type ('box' | 'image' | 'caption' | 'captiontag'), set by a WITH_IMAGE_LABELS trainer before backward
         # single_rank_group: reduce over a one-rank group as well (bench.py --force-pg: RCCL next to hipGraph capture on one GPU)
         self.active = self.world > 1 or (dist.is_initialized() and single_rank_group)
         self.reserved_cus = 0

@@ -103,9 +103,23 @@ class CustomRCNN(nn.Module):
     @configurable
     def __init__(self, *, backbone, proposal_generator, roi_heads, pixel_mean, pixel_std, input_format=None,
                  vis_period=0, fp16=False, with_image_labels=False, roi_head_name="", dataset_loss_weight=(),
-                 dynamic_classifier=False, num_sample_cats=50, num_classes=None, freq_weight=None, **unused):
+                 dynamic_classifier=False, num_sample_cats=50, num_classes=None, freq_weight=None, with_caption=False,
+                 sync_caption_batch=False, cap_batch_ratio=4, text_encoder=None, **unused):
         super().__init__()
         assert proposal_generator is not None
+        # MODEL.WITH_CAPTION behind MODEL.CAPTION_TRAIN (custom_rcnn.py:58-62): the model owns the frozen text encoder, state-dict names
+        # `text_encoder.*` as in the reference; SYNC_CAPTION_BATCH gathers the caption rows of every rank on every training step
+        self.with_caption, self.sync_caption_batch, self.cap_batch_ratio = bool(with_caption), bool(sync_caption_batch), int(cap_batch_ratio)
+        if self.with_caption:
+            if dynamic_classifier:
+                raise NotImplementedError("MODEL.DYNAMIC_CLASSIFIER with MODEL.WITH_CAPTION: the reference asserts the two apart")
+            if text_encoder is None:
+                raise ValueError("with_caption needs text_encoder (MODEL.TEXT_ENCODER_WEIGHTS / MODEL.TEXT_ENCODER_BPE)")
+            self.text_encoder = text_encoder
+            for v in self.text_encoder.parameters():
+                v.requires_grad = False
+        elif self.sync_caption_batch:
+            raise ValueError("sync_caption_batch needs with_caption (MODEL.SYNC_CAPTION_BATCH / MODEL.WITH_CAPTION)")
         # MODEL.DYNAMIC_CLASSIFIER (custom_rcnn.py:50-55): a vocabulary of num_sample_cats classes sampled per batch.  freq_weight is a
         # plain attribute, as in the reference: the state dict does not change
         self.dynamic_classifier = bool(dynamic_classifier)
@@ -144,6 +158,17 @@ class CustomRCNN(nn.Module):
             from ..roi_heads.detic_fast_rcnn import load_class_freq
             dyn = dict(dynamic_classifier=True, num_classes=cfg.MODEL.ROI_HEADS.NUM_CLASSES, num_sample_cats=cfg.MODEL.NUM_SAMPLE_CATS,
                        freq_weight=load_class_freq(cfg.MODEL.ROI_BOX_HEAD.CAT_FREQ_PATH, cfg.MODEL.ROI_BOX_HEAD.FED_LOSS_FREQ_WEIGHT))
+        from ...config.caption import check_model_keys as check_caption_keys, check_text_encoder_dim, with_caption
+        check_caption_keys(cfg)
+        if with_caption(cfg):
+            from ..text import build_text_encoder
+            # (the encoder's constructor draws initial values that the state dict then replaces: under a forked generator, so that the
+            # rest of the model initialises exactly as it does without the encoder)
+            with torch.random.fork_rng(devices=[]):
+                enc = build_text_encoder(cfg.MODEL.TEXT_ENCODER_WEIGHTS, cfg.MODEL.TEXT_ENCODER_BPE, geometry_from_weights=True)
+            check_text_encoder_dim(cfg, enc.embed_dim)
+            dyn = dict(dyn, with_caption=True, text_encoder=enc, sync_caption_batch=bool(cfg.MODEL.SYNC_CAPTION_BATCH),
+                       cap_batch_ratio=cfg.MODEL.CAP_BATCH_RATIO)
         backbone = build_backbone(cfg)
         shape = backbone.output_shape()
         return dict(**dyn, backbone=backbone, proposal_generator=build_proposal_generator(cfg, shape),
@@ -209,9 +234,28 @@ class CustomRCNN(nn.Module):
         types = set(x["ann_type"] for x in batched_inputs)
         assert len(types) == 1, "one annotation type per batch, got %s (DATALOADER.MULTI_DATASET_GROUPING)" % sorted(types)
         ann_type = types.pop()
-        if ann_type not in ("box", "image"):
-            raise NotImplementedError("ann_type %r: 'box' and 'image' are built (DATALOADER.DATASET_ANN)" % (ann_type,))
+        if ann_type not in ("box", "image") + (("caption", "captiontag") if self.with_caption else ()):
+            raise NotImplementedError("ann_type %r: 'box' and 'image' are built, 'caption' / 'captiontag' with MODEL.WITH_CAPTION behind "
+                                      "MODEL.CAPTION_TRAIN (DATALOADER.DATASET_ANN)" % (ann_type,))
         return ann_type
+
+    def _caption_features(self, batched_inputs, ann_type):
+        """custom_rcnn.py:148-157: one caption per sample drawn with torch.randint in batch order (the tokenizer's crop draws come after
+        them, inside the encoder), encoded to (B, D) fp32; under SYNC_CAPTION_BATCH the rank column appended and the rows of every
+        rank gathered -- every rank takes part on every training step, a step without captions sends zero rows and gets None."""
+        feats = None
+        if self.with_caption and "caption" in ann_type:
+            for x in batched_inputs:
+                if not x.get("captions"):
+                    raise KeyError("a %r batch needs `captions` (a non-empty list of strings) on every sample" % (ann_type,))
+            inds = [torch.randint(len(x["captions"]), (1,))[0].item() for x in batched_inputs]
+            feats = self.text_encoder([x["captions"][i] for i, x in zip(inds, batched_inputs)]).float()
+        if self.sync_caption_batch:
+            from ...layers.caption_ops import all_gather_rows, sync_caption_features
+            from ...utils import comm
+            feats = sync_caption_features(feats, ann_type, len(batched_inputs), comm.get_rank(), self.cap_batch_ratio, all_gather_rows,
+                                          dim=self.text_encoder.embed_dim, device=self.device)
+        return feats
 
     def _weight_by_source(self, batched_inputs, losses):
         """custom_rcnn.py:197-202: MODEL.DATASET_LOSS_WEIGHT multiplies every loss by the weight of the batch's `dataset_source`."""
@@ -255,14 +299,14 @@ class CustomRCNN(nn.Module):
         inds, cls_id_map, n = sample_classes(gt_classes, prob0, expo, C, self.num_classes, self.num_sample_cats)
         return DynamicVocab(inds, cls_id_map, n_host if (n_host is not None and torch.is_tensor(n)) else n, self.num_classes)
 
-    def _image_step_losses(self, images, features, gt_instances, classifier_info=(None, None, None)):
+    def _image_step_losses(self, images, features, gt_instances, classifier_info=(None, None, None), ann_type="image"):
         """An image-labelled batch (custom_rcnn.py:166-194): the proposal generator runs for its proposals only, without gradient
         tracking (no autograd graph is built or held) -- its losses are reported as exact zeros (the reference's `v * 0` of finite
         values), so neither its backward nor the early backward pass exist in this step; the RoI heads train the cascade's
         classifiers on the image labels."""
         with torch.no_grad():
             proposals, proposal_losses = self.proposal_generator(images, features, gt_instances)
-        proposals, detector_losses = self.roi_heads(images, features, proposals, gt_instances, ann_type="image",
+        proposals, detector_losses = self.roi_heads(images, features, proposals, gt_instances, ann_type=ann_type,
                                                     classifier_info=classifier_info)
         losses = dict(detector_losses)
         losses.update({k: v.detach().float().reshape(()) * 0.0 for k, v in proposal_losses.items()})
@@ -278,14 +322,18 @@ class CustomRCNN(nn.Module):
         from ...solver import join_transposes
         join_transposes()        # transposed weight images refreshed beside the backbone forward: first read by what follows
         grads_on = torch.is_grad_enabled() and all(f.requires_grad for f in features.values())
-        if ann_type == "image":
+        # after the backbone, before the proposal generator: the reference's position in torch's random stream (:148-157).  With
+        # SYNC_CAPTION_BATCH this gathers on every step, box steps included (their rows are zeros and the result is dropped)
+        caption_features = self._caption_features(batched_inputs, ann_type) if self.with_caption else None
+        if ann_type != "box":
             if only_gt_proposals:
                 raise NotImplementedError("only_gt_proposals (BSGAL's held-out pass) on an image-labelled batch")
             with torch.autocast("cuda", dtype=torch.bfloat16):
                 if grads_on:
                     fg, features = _shared_gradient_maps(features)
-                ci = (None, self._sample_cls_inds(gt_instances, "image"), None) if self.dynamic_classifier else (None, None, None)
-                proposals, losses = self._image_step_losses(images, features, gt_instances, ci)
+                ci = (None, self._sample_cls_inds(gt_instances, "image"), None) if self.dynamic_classifier else \
+                    (None, None, caption_features if "caption" in ann_type else None)
+                proposals, losses = self._image_step_losses(images, features, gt_instances, ci, ann_type)
             losses = self._weight_by_source(batched_inputs, losses)
             return (proposals, losses) if self.return_proposal else losses
         with torch.autocast("cuda", dtype=torch.bfloat16):

@@ -168,8 +168,13 @@ class DeticFastRCNNOutputLayers(nn.Module):
                  ignore_zero_cats=False, fed_loss_num_cat=50, prior_prob=0.01, cat_freq_path="",
                  fed_loss_freq_weight=0.5, use_zeroshot_cls=False, cls_score=None, divergen_box_loss=True, only_paste_sup=False,
                  image_label_loss="", image_loss_weight=0.1, add_image_box=False, with_softmax_prop=False, ws_prop_score=False,
-                 **unused):
+                 with_caption=False, caption_weight=1.0, neg_cap_weight=1.0, sync_caption_batch=False, **unused):
         super().__init__()
+        # MODEL.WITH_CAPTION behind MODEL.CAPTION_TRAIN (DG detic_fast_rcnn.py:364-375, :452-458, :469-506): caption scores and loss
+        self.with_caption, self.sync_caption_batch = bool(with_caption), bool(sync_caption_batch)
+        self.caption_weight, self.neg_cap_weight = float(caption_weight), float(neg_cap_weight)
+        if self.with_caption and not (use_zeroshot_cls and add_image_box):
+            raise ValueError("with_caption needs use_zeroshot_cls and add_image_box (MODEL.ROI_BOX_HEAD.USE_ZEROSHOT_CLS / ADD_IMAGE_BOX)")
         # WITH_IMAGE_LABELS (DG detic_fast_rcnn.py:342-434): "" = the predictor trains on box annotations only
         from ...config.image_labels import WSDDN_LOSSES, check_image_label_loss
         if image_label_loss:
@@ -232,8 +237,10 @@ class DeticFastRCNNOutputLayers(nn.Module):
     @classmethod
     def from_config(cls, cfg, input_shape, box2box_transform=None):
         h = cfg.MODEL.ROI_BOX_HEAD
+        from ...config.caption import with_caption
         from ...config.image_labels import check_model_keys
         check_model_keys(cfg)
+        caption = with_caption(cfg)
         ws_prop = bool(h.get("WS_PROP_SCORE", False))
         dyn_vocab = bool(cfg.MODEL.get("DYNAMIC_VOCAB", False))
         if dyn_vocab:
@@ -242,11 +249,12 @@ class DeticFastRCNNOutputLayers(nn.Module):
         if h.USE_ZEROSHOT_CLS:
             for key, on in (("MODEL.ROI_BOX_HEAD.WITH_SOFTMAX_PROP", h.WITH_SOFTMAX_PROP and not ws_prop),
                             ("MODEL.DYNAMIC_CLASSIFIER", cfg.MODEL.DYNAMIC_CLASSIFIER and not dyn_vocab),
-                            ("MODEL.WITH_CAPTION", cfg.MODEL.WITH_CAPTION)):
+                            ("MODEL.WITH_CAPTION", cfg.MODEL.WITH_CAPTION and not caption)):
                 if on:
                     raise NotImplementedError("%s is not built: the open-vocabulary classifier trains on box annotations and image labels "
                                               "(no dynamic classifier or caption losses; the proposal-score branch with "
-                                              "MODEL.ROI_BOX_HEAD.WS_PROP_SCORE True only)" % key)
+                                              "MODEL.ROI_BOX_HEAD.WS_PROP_SCORE True only; caption losses with MODEL.CAPTION_TRAIN True "
+                                              "only)" % key)
         return dict(input_shape=input_shape, cls_score=ZeroShotClassifier(cfg, input_shape) if h.USE_ZEROSHOT_CLS else None,
                     box2box_transform=box2box_transform or Box2BoxTransform(weights=h.BBOX_REG_WEIGHTS),
                     num_classes=cfg.MODEL.ROI_HEADS.NUM_CLASSES, cls_agnostic_bbox_reg=h.CLS_AGNOSTIC_BBOX_REG,
@@ -259,12 +267,14 @@ class DeticFastRCNNOutputLayers(nn.Module):
                     divergen_box_loss=cfg.MODEL.USE_DIVERGEN_BOX_LOSS and cfg.MODEL.get("USE_XPASTE_BOX_LOSS", True),
                     only_paste_sup=cfg.MODEL.get("ONLY_PASTE_SUP", False),
                     image_label_loss=h.IMAGE_LABEL_LOSS if cfg.WITH_IMAGE_LABELS else "", image_loss_weight=h.IMAGE_LOSS_WEIGHT,
-                    add_image_box=h.ADD_IMAGE_BOX, with_softmax_prop=bool(h.WITH_SOFTMAX_PROP) and ws_prop, ws_prop_score=ws_prop)
+                    add_image_box=h.ADD_IMAGE_BOX, with_softmax_prop=bool(h.WITH_SOFTMAX_PROP) and ws_prop, ws_prop_score=ws_prop,
+                    with_caption=caption, caption_weight=h.CAPTION_WEIGHT, neg_cap_weight=h.NEG_CAP_WEIGHT,
+                    sync_caption_batch=caption and bool(cfg.MODEL.SYNC_CAPTION_BATCH))
 
     def forward(self, x, classifier_info=(None, None, None), with_prop_scores=False):
         if x.dim() > 2:
             x = torch.flatten(x, start_dim=1)
-        if classifier_info[2] is not None:
+        if classifier_info[2] is not None and not self.with_caption:
             raise NotImplementedError("caption scores (classifier_info[2], MODEL.WITH_CAPTION) are not built: the box predictor "
                                       "trains on box annotations only")
         # DG :462-464 returns the proposal scores from every call and every caller but the WSDDN loss drops them: here they are computed
@@ -273,7 +283,15 @@ class DeticFastRCNNOutputLayers(nn.Module):
             raise RuntimeError("with_prop_scores on a predictor built without MODEL.ROI_BOX_HEAD.WITH_SOFTMAX_PROP")
         prop = (self.prop_score_rows(x),) if with_prop_scores else ()
         if self.use_zeroshot_cls:
-            return (self.cls_score(x, classifier=classifier_info[0]), self._bbox_pred_rows(x)) + prop
+            scores = self.cls_score(x, classifier=classifier_info[0])
+            if classifier_info[2] is not None:
+                # DG :452-459: the caption scores through the per-call classifier path, beside the class scores: (R, C + 1 + N); the rank
+                # column of a synced batch is cut off.  (A training step does not come here: _forward_image hands the projected rows to
+                # the fused caption loss and never forms these n x N scores)
+                cap = classifier_info[2]
+                cap = cap[:, :-1] if self.sync_caption_batch else cap
+                scores = torch.cat([scores, self.cls_score(x, classifier=cap.contiguous())], dim=1)
+            return (scores, self._bbox_pred_rows(x)) + prop
         if classifier_info[0] is not None:
             raise NotImplementedError("a per-call vocabulary (classifier_info[0]) needs MODEL.ROI_BOX_HEAD.USE_ZEROSHOT_CLS")
         y = self.forward_joint(x)
@@ -430,6 +448,22 @@ class DeticFastRCNNOutputLayers(nn.Module):
             st.put_scalar(name, DeferredScalar(lambda o, i=i: o[2 + i], out))
         zero = torch.zeros((), dtype=torch.float32, device=scores.device)
         return {"image_loss": loss, "loss_cls": zero, "loss_box_reg": zero.clone()}
+
+    def caption_losses(self, u, valid, counts, captions):
+        """DG detic_fast_rcnn.py:370-375, :420-423, :469-506 for one cascade stage of a caption batch, on the projected rows
+        u = cls_score.project(x) (R_alloc, D) and the step's PreparedCaptions: the BCE of the image box's caption logits (the last valid
+        row of every image) times CAPTION_WEIGHT, over B, times IMAGE_LOSS_WEIGHT -- the caption half of image_loss -- from one launch
+        (dgx_caption_loss); stats_l_caption stays on the device."""
+        from ...layers.caption_ops import caption_loss
+        from ...utils.events import DeferredScalar
+        if not self.with_caption:
+            raise RuntimeError("caption_losses on a predictor built without MODEL.WITH_CAPTION")
+        cs, B = self.cls_score, len(counts)
+        with torch.autocast("cuda", enabled=False):
+            loss, out, _ = caption_loss(u, cs.cls_bias if cs.use_bias else None, valid, counts, captions, cs.norm_temperature, cs.norm_weight,
+                                        self.caption_weight * self.image_loss_weight / B, self.caption_weight / B)
+        get_event_storage().put_scalar("stats_l_caption", DeferredScalar(lambda o: o[1], out))
+        return loss
 
     def no_grad_losses(self, predictions, proposals, classifier_info=(None, None, None)):
         """BS detic_fast_rcnn.py:268-352 for the sigmoid-CE recipe: the losses of the held-out pass over ground-truth

@@ -549,11 +549,34 @@ class DeticCascadeROIHeads(nn.Module):
             x = self.mask_pooler(feats, boxes, pad_to=64 if self.training else 0)
         return self.mask_head(x, instances)
 
-    def _forward_image(self, features, proposals, targets, classifier_info=(None, None, None)):
+    def _prepare_captions(self, classifier_info, B):
+        """classifier_info[2] of a caption step -- the (B, D) caption features of this rank, or the gathered (M Bcap, D + 1) matrix with
+        the rank column under MODEL.SYNC_CAPTION_BATCH -- as the rows the three stages' caption loss reads (one dgx_caption_prepare)."""
+        from ...layers.caption_ops import prepare_captions
+        from ...utils import comm
+        feats, pred = classifier_info[2], self.box_predictor[0]
+        if feats is None:
+            raise RuntimeError("a caption step needs the caption features (classifier_info[2]; MODEL.WITH_CAPTION)")
+        cs = pred.cls_score
+        sync = pred.sync_caption_batch
+        if not sync and feats.shape[0] != B:      # DG :493 `assert caption_score.shape[1] == B`
+            raise ValueError("%d caption rows for a batch of %d images (MODEL.SYNC_CAPTION_BATCH is off)" % (feats.shape[0], B))
+        rank = comm.get_rank() if sync else 0
+        if sync and (feats.shape[0] % B or B * (rank + 1) > feats.shape[0]):
+            raise ValueError("MODEL.SYNC_CAPTION_BATCH: %d gathered caption rows for batches of %d on rank %d" % (feats.shape[0], B, rank))
+        return prepare_captions(feats, cs.zs_weight.shape[0], cs.norm_weight, synced=sync, batch=B, rank=rank,
+                                neg_cap_weight=pred.neg_cap_weight)
+
+    def _forward_image(self, features, proposals, targets, classifier_info=(None, None, None), ann_type="image"):
         """One image-labelled batch (DG detic_roi_heads.py:214, :226-234, :320, :341-365): the first WS_NUM_PROPS proposals of every image
         [+ the image box] (dgx_ws_proposals), three stages WITHOUT matching -- pooler -> box head -> predictor as composed modules, the
         hand-over dgx_cascade_refine with zero ground truth (its labels are ignored, its valid_out feeds the next stage) -- and
-        image_label_losses per stage.  All lists keep their length, rows carry a validity byte: no device->host read."""
+        image_label_losses per stage.  All lists keep their length, rows carry a validity byte: no device->host read.
+        ann_type 'caption' / 'captiontag' (MODEL.WITH_CAPTION): each stage asks its classifier for the projected rows u = linear(x) and
+        hands them to the fused caption loss (predictor.caption_losses; the n x N caption scores are never formed).  On 'caption' that
+        is the whole image_loss: the class-logit GEMM and the normalisation of all rows are not launched -- nothing reads them -- and
+        stats_l_image with the five selection statistics are the reference's zeros; on 'captiontag' the configured image-label loss
+        reads the class scores of the same u and image_loss is the sum of the two."""
         import ctypes
         from ... import _lib as L
         from ...layers.image_label_ops import label_csr, ws_proposals
@@ -569,7 +592,12 @@ class DeticCascadeROIHeads(nn.Module):
         sizes = [p.image_size for p in proposals]
         prop, logits, pvalid, Ko = ws_proposals(boxes, scores, valid, sizes, self.ws_num_props, self.add_image_box, self.image_box_size)
         counts, R, dev = [Ko] * B, B * Ko, prop.device
-        csr = label_csr([t._pos_category_ids for t in targets], dev)
+        caption = ann_type in ("caption", "captiontag")
+        tags = ann_type != "caption"             # the image-label loss runs
+        captions = self._prepare_captions(classifier_info, B) if caption else None
+        if caption:
+            classifier_info = (classifier_info[0], classifier_info[1], None)
+        csr = label_csr([t._pos_category_ids for t in targets], dev) if tags else None
         from ...layers.dyn_vocab_ops import DynamicVocab
         dyn = classifier_info[1] if isinstance(classifier_info[1], DynamicVocab) else None
         if dyn is not None:
@@ -602,17 +630,33 @@ class DeticCascadeROIHeads(nn.Module):
             x = self.box_pooler.forward_rows(feats, prop, counts, pad_to=256)
             x = _ScaleGradient.apply(x, 1.0 / self.num_cascade_stages)
             pred = self.box_predictor[k]
-            out = pred(self.box_head[k](x), classifier_info, with_prop_scores=pred.wsddn)      # (the WSDDN loss reads predictions[2]; nothing else does)
-            sc, deltas = out[0][:R], out[1][:R]
+            u = None
+            if caption:
+                h = self.box_head[k](x)
+                h = torch.flatten(h, start_dim=1) if h.dim() > 2 else h
+                u = pred.cls_score.project(h)            # both consumers read u; autograd adds their two gradients
+                out = ((pred.cls_score.score(u, classifier_info[0]) if tags else None), pred._bbox_pred_rows(h))
+            else:
+                out = pred(self.box_head[k](x), classifier_info, with_prop_scores=pred.wsddn)      # (the WSDDN loss reads predictions[2]; nothing else does)
+            sc, deltas = (out[0][:R] if out[0] is not None else None), out[1][:R]
             ps = out[2][:R] if len(out) > 2 else None
             obs = self.__dict__.get("stage_observer")
             if obs is not None:      # tests: what this stage's image-label loss sees
-                obs(k, dict(boxes=prop, valid=pvalid, scores=sc, prop_scores=ps, counts=counts, image_sizes=sizes))
+                obs(k, dict(boxes=prop, valid=pvalid, scores=sc, prop_scores=ps, counts=counts, image_sizes=sizes, u=u, captions=captions))
             with st.name_scope("stage{}".format(k)):
                 if dyn is not None and len(targets[0]._pos_category_ids):
                     # DG :382-383, inside each predictor's image_label_losses: the first image's first label, before the remap
                     st.put_scalar("stats_label", float(targets[0]._pos_category_ids[0]))
-                sl = pred.image_label_losses(sc, pvalid, prop, counts, sizes, None, csr=csr, prop_scores=ps)
+                if tags:
+                    sl = pred.image_label_losses(sc, pvalid, prop, counts, sizes, None, csr=csr, prop_scores=ps)
+                else:                            # DG :374-375 `continue`: no label loss, the statistics stay at their initial zeros
+                    zero = torch.zeros((), dtype=torch.float32, device=dev)
+                    sl = {"image_loss": zero, "loss_cls": zero.clone(), "loss_box_reg": zero.clone()}
+                    for name in ("stats_l_image", "pool_stats", "stats_select_size", "stats_select_x", "stats_select_y", "stats_max_label_score"):
+                        st.put_scalar(name, 0.0)
+                if caption:
+                    cap_loss = pred.caption_losses(u, pvalid, counts, captions)
+                    sl["image_loss"] = sl["image_loss"] + cap_loss if tags else cap_loss
             losses.update({n + "_stage{}".format(k): v for n, v in sl.items()})
         out = ProposalBatch()
         for i, p in enumerate(proposals):
@@ -623,12 +667,14 @@ class DeticCascadeROIHeads(nn.Module):
                 classifier_info=(None, None, None), **kwargs):
         if self.training:
             if ann_type != "box":
-                if ann_type != "image" or not self.with_image_labels:
-                    raise NotImplementedError("ann_type %r: box batches, and image-labelled batches with WITH_IMAGE_LABELS, are built "
-                                              "(DATALOADER.DATASET_ANN 'box' / 'image')" % (ann_type,))
+                caption_ok = ann_type in ("caption", "captiontag") and self.box_predictor[0].with_caption
+                if (ann_type != "image" and not caption_ok) or not self.with_image_labels:
+                    raise NotImplementedError("ann_type %r: box batches, image-labelled batches with WITH_IMAGE_LABELS and, with "
+                                              "MODEL.WITH_CAPTION behind MODEL.CAPTION_TRAIN, caption batches are built "
+                                              "(DATALOADER.DATASET_ANN 'box' / 'image' / 'caption' / 'captiontag')" % (ann_type,))
                 self.__dict__.pop("_before_host_read", None)      # (no sampler, no device->host read to hide work behind)
                 self.__dict__.pop("_gt_batch", None)
-                proposals, losses = self._forward_image(features, proposals, targets, classifier_info)
+                proposals, losses = self._forward_image(features, proposals, targets, classifier_info, ann_type)
                 if self.mask_on:        # DG detic_roi_heads.py:329-332: the mask head is not run
                     losses["loss_mask"] = torch.zeros((1,), device=proposals[0].objectness_logits.device)[0]
                 return proposals, losses

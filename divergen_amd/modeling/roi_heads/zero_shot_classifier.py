@@ -140,13 +140,24 @@ class ZeroShotClassifier(nn.Module):
     def forward(self, x, classifier=None):
         """x (R, in) -> logits (R, C + 1); with `classifier` (C', D), the per-call vocabulary of detic_fast_rcnn.py:445-446, its
         rows are normalised per call and the result is (R, C').  `classifier` may also be the prepared operand pair of such a
-        vocabulary (layers/dyn_vocab_ops.PreparedVocab, built by dgx_zs_gather: already normalised, cast, padded and transposed)."""
+        vocabulary (layers/dyn_vocab_ops.PreparedVocab, built by dgx_zs_gather: already normalised, cast, padded and transposed).
+        The composition of its two halves: `project` and `score`."""
+        return self.score(self.project(x), classifier)
+
+    def project(self, x):
+        """The first half of forward: u = linear(x), (R, D).  A caption step hands these rows to the caption loss as well
+        (layers/caption_ops.caption_loss), which normalises the one row per image it reads itself."""
+        if not x.is_cuda:
+            return F.linear(x, self.linear.weight, self.linear.bias)      # host logic tests: the reference's arithmetic in torch
+        return self.linear(x)
+
+    def score(self, h, classifier=None):
+        """The second half of forward: the projected rows normalised and scaled by NORM_TEMP, scored against the vocabulary."""
         from ...layers.dyn_vocab_ops import PreparedVocab
         prepared = classifier if isinstance(classifier, PreparedVocab) else None
-        if not x.is_cuda:
+        if not h.is_cuda:
             if prepared is not None:
                 raise RuntimeError("a prepared vocabulary (PreparedVocab) holds GPU operand images; CPU tensors take the raw `classifier` rows")       # host logic tests: the reference's arithmetic in torch
-            h = F.linear(x, self.linear.weight, self.linear.bias)
             if classifier is not None:
                 zs = classifier.permute(1, 0).contiguous()
                 zs = F.normalize(zs, p=2, dim=0) if self.norm_weight else zs
@@ -156,7 +167,6 @@ class ZeroShotClassifier(nn.Module):
                 h = self.norm_temperature * F.normalize(h, p=2, dim=1)
             y = torch.mm(h, zs)
             return y + self.cls_bias if self.use_bias else y
-        h = self.linear(x)
         if self.norm_weight:
             h = l2_normalize_rows(h, self.norm_temperature)
         elif h.dtype != BF16:

@@ -267,15 +267,29 @@ class CLIPTEXT(nn.Module):
 _DROPPED = ("logit_scale", "input_resolution", "context_length", "vocab_size")
 
 
-def build_text_encoder(weights_path, bpe_path=None, **kwargs):
+def state_dict_geometry(sd):
+    """CLIPTEXT's constructor arguments read from the shapes of a text state dict: vocabulary, width, layers, context, embed dim;
+    heads = width / 64 (the attention kernel's head)."""
+    vocab, width = sd["token_embedding.weight"].shape
+    blocks = set(k.split(".")[2] for k in sd if k.startswith("transformer.resblocks."))
+    return dict(embed_dim=int(sd["text_projection"].shape[1]), context_length=int(sd["positional_embedding"].shape[0]),
+                vocab_size=int(vocab), transformer_width=int(width), transformer_heads=int(width) // text_ops.HEAD_DIM,
+                transformer_layers=len(blocks))
+
+
+def build_text_encoder(weights_path, bpe_path=None, geometry_from_weights=False, **kwargs):
     """CLIPTEXT with the state dict at `weights_path` loaded strictly: clip's ViT-B/32 state dict with
-    `visual.*` and the four scalars deleted, as the reference leaves it (keys still present are dropped the same way)."""
+    `visual.*` and the four scalars deleted, as the reference leaves it (keys still present are dropped the same way).
+    geometry_from_weights: the constructor arguments come from the state dict's shapes (state_dict_geometry) instead of the ViT-B/32
+    defaults -- the model's own encoder (MODEL.TEXT_ENCODER_WEIGHTS) is built this way."""
     if not weights_path:
         raise ValueError("weights_path is empty: this build never downloads CLIP; give the path of the text encoder's "
                          "state dict")
     sd = torch.load(weights_path, map_location="cpu")
     sd = sd.get("state_dict", sd) if isinstance(sd, dict) else sd.state_dict()
     sd = {k: v for k, v in sd.items() if k not in _DROPPED and not k.startswith("visual.")}
+    if geometry_from_weights:
+        kwargs = dict(state_dict_geometry(sd), **kwargs)
     model = CLIPTEXT(bpe_path=bpe_path, **kwargs)
     model.load_state_dict(sd)
     return model.eval()

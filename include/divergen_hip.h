@@ -910,6 +910,35 @@ int dgx_wsddn_loss(const void* logits, int64_t ld_logits, const void* prop, int6
                    int64_t ld_dprop, float* ws, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * dgx_caption_prepare / dgx_caption_loss (detic_fast_rcnn.py:469-506 `_caption_loss` inside :342-434 `image_label_losses`, the caption
+ * half of `forward` :452-458 and of zero_shot_classifier.py:73-87): the caption loss of an image-labelled step without the n x N
+ * caption scores.  Conventions of dgx_wsddn_loss: B <= 32, HOST array row0, a validity byte per row.
+ *   dgx_caption_prepare: cap f32 (N, ld_cap), ld_cap >= D (D + 1 when the gathered rows carry the rank column: it is cut off) ->
+ *     out f32 (N, D) dense, row / max(|row|, 1e-12) when norm_weight (F.normalize), else a copy.  A zero row stays zero.
+ *   dgx_caption_loss: u (R_alloc, ld_u) f32|bf16, the PROJECTED box features (cls_score.linear(x)), columns [0, D) read; cap the
+ *     prepared rows (N, D).  Per image b the last row of [row0[b], row0[b+1]) whose validity byte is set (valid NULL = all):
+ *       h = norm_weight ? temp * u / max(|u|, 1e-12) : u;   s_j = h . cap_j + (cls_bias ? cls_bias[0] : 0), fp32 accumulation;
+ *       l_b = sum_j w_j (max(s_j, 0) - s_j t_j + log1p(exp(-|s_j|))),  t_j = [j == target0 + b],  w_j = t_j ? 1 : neg_weight.
+ *     An image without a valid row contributes 0 and still counts.  out4 = {scale * sum_b l_b, stat_scale * sum_b l_b, 0, 0}
+ *     (the caller passes scale = CAPTION_WEIGHT * IMAGE_LOSS_WEIGHT / B, stat_scale = CAPTION_WEIGHT / B: image_loss and
+ *     stats_l_caption); sel i32 (B) = the chosen row relative to its image, -1 = none.
+ *     Forward launch (du = NULL): out4, sel; leaves in ws the logit gradients scale * w_j (sigmoid(s_j) - t_j), (B, N), and their sum.
+ *     Gradient launch (du != NULL; sel, ws of the forward launch): du (R_alloc, ld_du), dtype of u, ld_du % 8 == 0, EVERY element
+ *     written: exact zeros outside the chosen rows and in columns >= D; in a chosen row, with dh = sum_j g_j cap_j and
+ *     K = upstream[0] (f32 device scalar, NULL = 1):  norm_weight, |u| > 1e-12: K temp (dh - uhat (uhat . dh)) / |u|;  norm_weight,
+ *     otherwise: K temp dh / 1e-12;  no norm_weight: K dh.  dbias f32 (1) or NULL = K * the sum of all logit gradients.
+ *   Refused with DGX_ERR_BAD_ARG, nothing launched: B outside 1..32, D % 8 != 0 or outside 8..4096, N <= 0, target0 < 0 or
+ *   target0 + B > N, row0 not ascending from 0 or row0[B] > R_alloc, a NULL pointer that would be read or written, u / cap / du not
+ *   16-byte aligned (pointer and row pitch).  No floating-point atomics, every sum in a fixed order: two runs give the same bits.
+ *   ws f32: dgx_caption_workspace_floats(B, N) floats. */
+int dgx_caption_prepare(const float* cap, int64_t ld_cap, int N, int D, int norm_weight, float* out, void* stream);
+int64_t dgx_caption_workspace_floats(int B, int N);
+int dgx_caption_loss(const void* u, int64_t ld_u, int64_t R_alloc, const uint8_t* valid, int B, const int* row0, const float* cap,
+                     int N, int D, int target0, float temp, int norm_weight, const float* cls_bias, float neg_weight, float scale,
+                     float stat_scale, const float* upstream, int32_t* sel, float* out4, float* ws, void* du, int64_t ld_du,
+                     float* dbias, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Exact (erf) GELU of the Swin MLP on bf16 activations (swintransformer.py:40-46, nn.GELU()).
  *   dgx_gelu_fwd: y = gelu(x), n elements (n % 8 == 0).
  *   dgx_gelu_bwd_colsum: dx (M, N) = dy * gelu'(x) and, when bias_grad != NULL, bias_grad (N) = beta*bias_grad +

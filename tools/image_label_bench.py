@@ -14,6 +14,14 @@ next to the bytes they must move:
 
     python tools/image_label_bench.py --vocab 22047              # static: R x (N + 1) logits per cascade stage
     python tools/image_label_bench.py --vocab 22047 --dynamic    # dynamic: R x (NUM_SAMPLE_CATS + 1)
+
+--caption turns on MODEL.CAPTION_TRAIN + MODEL.WITH_CAPTION on an open-vocabulary classifier (--vocab, 1203 when not given) with a
+randomly initialised text encoder of the ViT-B/32 geometry (--text-layers to shrink it) and a generated merges file, and times a
+'caption' step and a 'captiontag' step next to the box and image steps; from one profiled step of each it reports the device time and
+the launch count of the kernels of csrc/caption_loss.hip.  --sync adds MODEL.SYNC_CAPTION_BATCH (CAP_BATCH_RATIO 1) in a one-rank
+process group: the gather runs on every step, box steps included.
+
+    python tools/image_label_bench.py --caption [--sync]
 """
 import argparse
 import json
@@ -38,7 +46,16 @@ def main():
     ap.add_argument("--vocab", type=int, default=0)
     ap.add_argument("--dynamic", action="store_true")
     ap.add_argument("--sample-cats", type=int, default=50)
+    ap.add_argument("--caption", action="store_true")
+    ap.add_argument("--sync", action="store_true")
+    ap.add_argument("--text-layers", type=int, default=12)
     a = ap.parse_args()
+    if a.sync and not a.caption:
+        ap.error("--sync needs --caption")
+    if a.caption and a.dynamic:
+        ap.error("--caption and --dynamic exclude each other (the reference asserts the two apart)")
+    if a.caption and not a.vocab:
+        a.vocab = 1203
     if a.dynamic and not a.vocab:
         ap.error("--dynamic needs --vocab N")
     from divergen_amd.config import get_cfg
@@ -64,6 +81,25 @@ def main():
                              "MODEL.ROI_BOX_HEAD.CAT_FREQ_PATH", freq])
         if a.dynamic:
             cfg.merge_from_list(["MODEL.DYNAMIC_VOCAB", True, "MODEL.DYNAMIC_CLASSIFIER", True, "MODEL.NUM_SAMPLE_CATS", a.sample_cats])
+    if a.caption:
+        import gzip
+        from divergen_amd.modeling.text import CLIPTEXT
+        tmp = tempfile.mkdtemp()
+        weights, bpe = os.path.join(tmp, "clip_text.pth"), os.path.join(tmp, "merges.txt.gz")
+        with gzip.open(bpe, "wb") as f:
+            f.write("\n".join(["#version: bench", "l o", "lo w</w>", "e r</w>", "n e", "ne w", "new er</w>"]).encode("utf-8"))
+        torch.manual_seed(1)
+        torch.save(dict(CLIPTEXT(transformer_layers=a.text_layers).state_dict()), weights)
+        cfg.merge_from_list(["MODEL.CAPTION_TRAIN", True, "MODEL.WITH_CAPTION", True, "MODEL.TEXT_ENCODER_WEIGHTS", weights,
+                             "MODEL.TEXT_ENCODER_BPE", bpe, "MODEL.SYNC_CAPTION_BATCH", a.sync, "MODEL.CAP_BATCH_RATIO", 1 if a.sync else 4])
+        if a.sync:
+            import socket
+            import torch.distributed as dist
+            with socket.socket() as sk:
+                sk.bind(("127.0.0.1", 0))
+                port = sk.getsockname()[1]
+            os.environ.setdefault("NCCL_MAX_NCHANNELS", "16")
+            dist.init_process_group("nccl", init_method="tcp://127.0.0.1:%d" % port, rank=0, world_size=1)
     wsddn = a.loss in ("wsddn", "wsod")
     if wsddn:
         cfg.merge_from_list(["MODEL.ROI_BOX_HEAD.WS_PROP_SCORE", True, "MODEL.ROI_BOX_HEAD.WITH_SOFTMAX_PROP", True])
@@ -81,6 +117,13 @@ def main():
                          gt_masks=BitMasks(torch.zeros(0, h, w, dtype=torch.bool, device="cuda")))
         img.append(dict(d, instances=inst, ann_type="image", pos_category_ids=[(7 * i + k) % C for k in range(1 + i % 3)], dataset_source=1))
 
+    steps = [("box", box), ("image", img)]
+    if a.caption:
+        words = ("low", "lower", "newer", "a", "new", "row", "of", "lows")
+        caps = [[" ".join(words[(3 * i + j + k) % len(words)] for k in range(4 + j)) for j in range(1 + i % 3)] for i in range(a.batch)]
+        steps.append(("caption", [dict(d, ann_type="caption", pos_category_ids=[], captions=c) for d, c in zip(img, caps)]))
+        steps.append(("captiontag", [dict(d, ann_type="captiontag", captions=c) for d, c in zip(img, caps)]))
+
     def step(batch):
         opt.zero_grad()
         total_loss(model(batch)).backward()
@@ -90,7 +133,7 @@ def main():
     if a.vocab:
         out.update(vocab=a.vocab, dynamic=a.dynamic, sample_cats=a.sample_cats if a.dynamic else None)
     with EventStorage(0):
-        for name, batch in (("box", box), ("image", img)):
+        for name, batch in steps:
             for _ in range(3):
                 step(batch)
             torch.cuda.synchronize()
@@ -101,6 +144,22 @@ def main():
             e1.record()
             torch.cuda.synchronize()
             out["ms_per_%s_step" % name] = round(e0.elapsed_time(e1) / a.steps, 3)
+        if a.caption:
+            from torch.profiler import ProfilerActivity, profile
+            out.update(caption=True, sync=a.sync, text_layers=a.text_layers)
+            kernels = ("caption_prepare_kernel", "caption_fwd_kernel", "caption_fold_kernel", "caption_bwd_kernel")
+            for name, batch in steps[2:]:
+                with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                    step(batch)
+                    torch.cuda.synchronize()
+                us, calls = {}, {}
+                for ev in prof.events():
+                    for k in kernels:
+                        if k in ev.name:
+                            us[k] = us.get(k, 0.0) + ev.device_time_total
+                            calls[k] = calls.get(k, 0) + 1
+                out["caption_us_per_%s_step" % name] = {k: round(v, 2) for k, v in us.items()}
+                out["caption_launches_per_%s_step" % name] = calls
         if a.dynamic:
             from torch.profiler import ProfilerActivity, profile
             kernels = ("dyn_class_sample_kernel", "zs_gather_kernel", "remap_labels_kernel", "zs_logits_f32_kernel")
@@ -142,6 +201,9 @@ def main():
             if us:
                 out["wsddn_gb_per_s"] = round(nbytes / (sum(us.values()) / stages * 1e-6) / 1e9, 1)
     print(json.dumps(out))
+    if a.sync:
+        import torch.distributed as dist
+        dist.destroy_process_group()
 
 
 if __name__ == "__main__":
