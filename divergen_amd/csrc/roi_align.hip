@@ -10,7 +10,9 @@
 #include "dgx_common.h"
 #include <stdlib.h>
 
-#define MAX_LEVELS 4
+#include "roi_tables.h"
+using namespace roitab;
+
 struct PoolLevels {
     const void* feat[MAX_LEVELS];
     float* grad[MAX_LEVELS];
@@ -19,55 +21,6 @@ struct PoolLevels {
     int num_levels, min_level;
 };
 
-struct Taps { int pos[4]; float w[4]; };
-
-__device__ __forceinline__ bool bilinear_taps(int H, int W, float y, float x, Taps& t) {
-    if (y < -1.0f || y > (float)H || x < -1.0f || x > (float)W) return false;
-    if (y <= 0) y = 0;
-    if (x <= 0) x = 0;
-    int y_low = (int)y, x_low = (int)x, y_high, x_high;
-    if (y_low >= H - 1) { y_high = y_low = H - 1; y = (float)y_low; } else y_high = y_low + 1;
-    if (x_low >= W - 1) { x_high = x_low = W - 1; x = (float)x_low; } else x_high = x_low + 1;
-    const float ly = y - y_low, lx = x - x_low, hy = 1.0f - ly, hx = 1.0f - lx;
-    t.pos[0] = y_low * W + x_low;   t.w[0] = hy * hx;
-    t.pos[1] = y_low * W + x_high;  t.w[1] = hy * lx;
-    t.pos[2] = y_high * W + x_low;  t.w[2] = ly * hx;
-    t.pos[3] = y_high * W + x_high; t.w[3] = ly * lx;
-    return true;
-}
-
-struct RoiGeom { float sw, sh, bin_w, bin_h; int gw, gh; float count; int b; };
-
-__device__ __forceinline__ RoiGeom roi_geom(const float* roi, float scale, int ph, int pw, int sampling_ratio, bool aligned) {
-    RoiGeom G;
-    G.b = (int)roi[0];
-    const float off = aligned ? 0.5f : 0.0f;
-    G.sw = roi[1] * scale - off;
-    G.sh = roi[2] * scale - off;
-    const float ew = roi[3] * scale - off, eh = roi[4] * scale - off;
-    float rw = ew - G.sw, rh = eh - G.sh;
-    if (!aligned) { rw = fmaxf(rw, 1.0f); rh = fmaxf(rh, 1.0f); }
-    G.bin_h = rh / (float)ph;
-    G.bin_w = rw / (float)pw;
-    G.gh = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rh / (float)ph);
-    G.gw = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rw / (float)pw);
-    G.count = (float)max(G.gh * G.gw, 1);
-    return G;
-}
-
-// level = floor(canonical_level + log2(sqrt(area)/224 + 1e-8)) clamped (poolers.py:50-58); evaluated
-// with exact power-of-two comparisons instead of log2 so it cannot straddle an integer.
-__device__ __forceinline__ int assign_level(const float* roi, int min_level, int num_levels) {
-    const float area = (roi[3] - roi[1]) * (roi[4] - roi[2]);
-    float t = sqrtf(area) / 224.0f + 1e-8f;
-    int lv = 4;
-    if (!(t > 0.0f)) return 0;  // degenerate / NaN: lowest level
-    while (t >= 2.0f && lv < 64) { t *= 0.5f; ++lv; }
-    while (t < 1.0f && lv > -64) { t *= 2.0f; --lv; }
-    lv -= min_level;
-    return lv < 0 ? 0 : (lv >= num_levels ? num_levels - 1 : lv);
-}
-
 template <typename T> __device__ __forceinline__ float ldf(const T* p);
 template <> __device__ __forceinline__ float ldf<float>(const float* p) { return *p; }
 template <> __device__ __forceinline__ float ldf<uint16_t>(const uint16_t* p) { return bf2f(*p); }
@@ -75,36 +28,7 @@ template <typename T> __device__ __forceinline__ void stf(T* p, float v);
 template <> __device__ __forceinline__ void stf<float>(float* p, float v) { *p = v; }
 template <> __device__ __forceinline__ void stf<uint16_t>(uint16_t* p, float v) { *p = f2bf(v); }
 
-// Separable form.  The bilinear weight of a sample on a pixel is hat(y)*hat(x) and a bin's samples
-// form a tensor grid, so the total weight a bin puts on pixel (r,q) is WY[i][r]*WX[j][q] with 1-D
-// tables built once per RoI in LDS (same clamping / validity rules as the per-sample form).  A bin
-// then touches each pixel of its footprint once -- (bin_h+1)(bin_w+1) taps instead of
-// 4*ceil(bin_h)*ceil(bin_w) -- and backward issues one atomic per footprint pixel per bin.
-struct Span { int base, n; };
-
-__device__ __forceinline__ void build_axis_table(float* Wt, Span* sp, int nb, int stride_tbl, float start, float bin,
-                                                 int g, int extent, int tid, int tid0) {
-    const int i = tid - tid0;
-    if (i < 0 || i >= nb) return;
-    float* w = Wt + i * stride_tbl;
-    for (int k = 0; k < stride_tbl; ++k) w[k] = 0.0f;
-    int base = -1, hi = -1;
-    for (int s = 0; s < g; ++s) {
-        float y = start + i * bin + ((float)s + 0.5f) * bin / (float)g;
-        if (y < -1.0f || y > (float)extent) continue;
-        if (y <= 0) y = 0;
-        int lo = (int)y, up;
-        if (lo >= extent - 1) { up = lo = extent - 1; y = (float)lo; } else up = lo + 1;
-        const float l = y - lo, h = 1.0f - l;
-        if (base < 0) base = lo;
-        w[lo - base] += h;
-        w[up - base] += l;
-        hi = up;
-    }
-    sp[i].base = base < 0 ? 0 : base;
-    sp[i].n = base < 0 ? 0 : hi - base + 1;
-}
-
+// Separable form: the 1-D weight tables of roi_tables.h (build_axis_table), one RoI per workgroup.
 // grid (R, nsplit): block handles bins [split*bpb, ...).  NCHW output goes through an LDS
 // transpose so that the (C, ph*pw) tile of a RoI is written as one contiguous run.
 template <typename T, bool BWD>
@@ -302,10 +226,6 @@ __global__ __launch_bounds__(256) void roi_align_vec_kernel(PoolLevels L, const 
 //   d feat[y][x][c] = sum_r sum_i WY_r[i][y] * ( sum_j WX_r[j][x] / count_r * d out[r][i][j][c] )
 // in registers.  Every gradient pixel is written exactly once, in the output dtype: no atomics, no zero fill, no fp32
 // staging map, and the summation order is fixed by the RoI order (bit-reproducible from run to run).
-#define GT_TH 8
-#define GT_QB 8
-#define GT_PMAX 16
-#define GT_TWMAX 32
 struct GatherP {
     void* out[MAX_LEVELS];
     int H[MAX_LEVELS], W[MAX_LEVELS];
@@ -316,22 +236,6 @@ struct GatherP {
     float gscale;        // factor on this pooling's contribution (the cascade's _ScaleGradient on the pooled features), folded into the x table
 };
 struct GatherMeta { int r, i_lo, i_hi; float sw, bin_w; };
-
-__device__ __forceinline__ void gather_axis_rows(float* w, int nw, int i, float start, float bin, int g, int extent, int p0) {
-    for (int k = 0; k < nw; ++k) w[k] = 0.0f;
-    for (int s = 0; s < g; ++s) {
-        float y = start + i * bin + ((float)s + 0.5f) * bin / (float)g;
-        if (y < -1.0f || y > (float)extent) continue;
-        if (y <= 0) y = 0;
-        int lo = (int)y, up;
-        if (lo >= extent - 1) { up = lo = extent - 1; y = (float)lo; } else up = lo + 1;
-        const float l = y - lo, h = 1.0f - l;
-        if ((unsigned)(lo - p0) < (unsigned)nw) w[lo - p0] += h;
-        if ((unsigned)(up - p0) < (unsigned)nw) w[up - p0] += l;
-    }
-}
-
-__device__ __forceinline__ int clamp_bin(float v, int hi) { return (int)fminf(fmaxf(v, 0.0f), (float)hi); }
 
 template <typename T, int TH>
 __global__ __launch_bounds__(256) void roi_pool_bwd_gather_kernel(GatherP P, const float* __restrict__ rois, const T* __restrict__ go) {
@@ -366,9 +270,7 @@ __global__ __launch_bounds__(256) void roi_pool_bwd_gather_kernel(GatherP P, con
             const int lvl = P.num_levels > 1 ? assign_level(roi, P.min_level, P.num_levels) : 0;
             if ((int)roi[0] == n && lvl == l) {
                 const RoiGeom G = roi_geom(roi, scale, ph, pw, P.sampling_ratio, P.aligned != 0);
-                // a sample at y weighs rows floor(y) and floor(y)+1 (after clamping into the map): rows within [y-1, y+1]
-                hit = G.gh > 0 && G.gw > 0 && G.sh - 1.0f <= (float)(y0 + TH - 1) && G.sh + G.bin_h * ph + 1.0f >= (float)y0 &&
-                      G.sw - 1.0f <= (float)(x0 + TW - 1) && G.sw + G.bin_w * pw + 1.0f >= (float)x0;
+                hit = gather_hit(G, ph, pw, y0, x0, TH, TW);
             }
         }
         const unsigned long long m = __ballot(hit);
@@ -397,11 +299,8 @@ __global__ __launch_bounds__(256) void roi_pool_bwd_gather_kernel(GatherP P, con
                     if (t5 == 0) {
                         GatherMeta mt;
                         mt.r = rr; mt.sw = G.sw; mt.bin_w = G.bin_w;
-                        mt.i_lo = 0; mt.i_hi = ph;
-                        if (G.bin_h > 0.0f) {   // bins whose interval meets [y0 - 1, y0 + TH], one bin of slack either side
-                            mt.i_lo = clamp_bin(floorf(((float)(y0 - 1) - G.sh) / G.bin_h) - 1.0f, ph);
-                            mt.i_hi = clamp_bin(floorf(((float)(y0 + TH) - G.sh) / G.bin_h) + 2.0f, ph);
-                        }
+                        // bins whose interval meets [y0 - 1, y0 + TH], one bin of slack either side
+                        gather_bin_range((float)(y0 - 1), (float)(y0 + TH), G.sh, G.bin_h, ph, mt.i_lo, mt.i_hi);
                         meta[q] = mt;
                     }
                 }
@@ -409,12 +308,9 @@ __global__ __launch_bounds__(256) void roi_pool_bwd_gather_kernel(GatherP P, con
             __syncthreads();
             for (int q = 0; q < nq; ++q) {
                 const GatherMeta mt = meta[q];
-                int j_lo = 0, j_hi = pw;
-                if (mt.bin_w > 0.0f) {
-                    const float xf = (float)(x0 + tx);
-                    j_lo = clamp_bin(floorf((xf - 1.0f - mt.sw) / mt.bin_w) - 1.0f, pw);
-                    j_hi = clamp_bin(floorf((xf + 1.0f - mt.sw) / mt.bin_w) + 2.0f, pw);
-                }
+                int j_lo, j_hi;
+                const float xf = (float)(x0 + tx);
+                gather_bin_range(xf - 1.0f, xf + 1.0f, mt.sw, mt.bin_w, pw, j_lo, j_hi);
                 const T* gr = go + (int64_t)mt.r * bins * C + 8 * cv;
                 for (int i = mt.i_lo; i < mt.i_hi; ++i) {
                     float wy[TH];
@@ -486,29 +382,15 @@ static int launch_gather(GatherP& P, const float* rois, const void* go, int dtyp
     if (!rois && P.R > 0) return DGX_ERR_BAD_ARG;
     if (!go && P.R > 0) return DGX_ERR_BAD_ARG;
     const int C = P.C;
-    if (C <= 0 || (C & 7) || 256 % (C >> 3) || 256 / (C >> 3) > GT_TWMAX || P.ph <= 0 || P.pw <= 0 || P.ph > GT_PMAX || P.pw > GT_PMAX)
-        return DGX_ERR_UNSUPPORTED;
+    if (!gather_supported(C, P.ph, P.pw)) return DGX_ERR_UNSUPPORTED;
     if (((uintptr_t)go & 15) != 0) return DGX_ERR_UNSUPPORTED;
-    const int TW = 256 / (C >> 3);
-    // tile height: 8 rows, or 4 when that is what it takes to give every CU a tile (a tile's workgroup walks the RoIs that reach it
-    // one after the other: with the RoI heads' three levels at 1024^2 x 2 images the 32 tiles of the coarsest level take most of the
-    // boxes of an untrained model each, while 650 small-level tiles finish early -- 4-row tiles halve the longest walk's work)
-    int th = GT_TH;
-    {
-        int64_t t8 = 0;
-        for (int l = 0; l < P.num_levels; ++l) t8 += (int64_t)P.N * ((P.W[l] + TW - 1) / TW) * ((P.H[l] + 7) / 8);
-        if (t8 < 4 * 256) th = 4;
-    }
-    int total = 0;
-    for (int l = 0; l < P.num_levels; ++l) {
+    for (int l = 0; l < P.num_levels; ++l)
         if (!P.out[l] || ((uintptr_t)P.out[l] & 15)) return P.out[l] ? DGX_ERR_UNSUPPORTED : DGX_ERR_BAD_ARG;
-        P.tile0[l] = total;
-        P.tiles_x[l] = (P.W[l] + TW - 1) / TW;
-        P.tiles_y[l] = (P.H[l] + th - 1) / th;
-        total += P.N * P.tiles_x[l] * P.tiles_y[l];
-    }
-    P.tile0[P.num_levels] = total;
-    P.total = total;
+    const GatherPlan pl = plan_gather(P.H, P.W, P.num_levels, P.N, C);
+    for (int l = 0; l < P.num_levels; ++l) { P.tile0[l] = pl.tile0[l]; P.tiles_x[l] = pl.tiles_x[l]; P.tiles_y[l] = pl.tiles_y[l]; }
+    P.tile0[P.num_levels] = pl.total;
+    P.total = pl.total;
+    const int th = pl.th, total = pl.total;
     if (total <= 0) return DGX_OK;
     if (dtype == DGX_BF16) {
         if (th == 4) hipLaunchKernelGGL((roi_pool_bwd_gather_kernel<uint16_t, 4>), dim3(total), dim3(256), 0, (hipStream_t)stream, P, rois, (const uint16_t*)go);
@@ -525,31 +407,17 @@ static int launch_pool(bool fwd, const PoolLevels& L, const float* rois, const v
                        int R, int ph, int pw, int sampling_ratio, int aligned, int out_nhwc, int dtype, void* stream) {
     if (R <= 0) return DGX_OK;
     if (!rois || !io || C <= 0 || ph <= 0 || pw <= 0 || ph > 64 || pw > 64) return DGX_ERR_BAD_ARG;
-    const int bins = ph * pw;
-    int spy = 0, spx = 0;
-    for (int l = 0; l < L.num_levels; ++l) { spy = L.H[l] > spy ? L.H[l] : spy; spx = L.W[l] > spx ? L.W[l] : spx; }
-    spy += 1; spx += 1;
-    const size_t tbl = (size_t)(ph * spy + pw * spx) * 4 + (size_t)(ph + pw) * sizeof(Span);
-    int bpb, nsplit;
-    if (out_nhwc) {
-        nsplit = R >= 2048 ? 1 : (R >= 512 ? 2 : 4);
-        if (nsplit > bins) nsplit = bins;
-        bpb = (bins + nsplit - 1) / nsplit;
-    } else {
-        if (tbl + (size_t)C * 4 > 64 * 1024) return DGX_ERR_UNSUPPORTED;
-        bpb = (int)((64 * 1024 - tbl) / ((size_t)C * 4));
-        if (bpb > bins) bpb = bins;
-    }
-    nsplit = (bins + bpb - 1) / bpb;
-    const size_t sm = tbl + (out_nhwc ? 0 : (size_t)bpb * C * 4);
-    if (sm > 64 * 1024) return DGX_ERR_UNSUPPORTED;
-    dim3 grid(R, nsplit), block(256);
+    const PoolPlan pl = plan_pool(L.H, L.W, L.num_levels, C, R, ph, pw, out_nhwc);
+    if (!pl.ok) return DGX_ERR_UNSUPPORTED;
+    const int spy = pl.spy, spx = pl.spx, bpb = pl.bpb;
+    const size_t tbl = pl.tbl, sm = pl.sm;
+    dim3 grid(R, pl.nsplit), block(256);
     hipStream_t st = (hipStream_t)stream;
-    if (out_nhwc && (C & 7) == 0 && C <= 2048 && 256 % (C >> 3) == 0) {   // 8 channels per lane, several bins in flight
-        bool aligned16 = true;
+    {
+        bool aligned16 = ((uintptr_t)io & 15) == 0;
         for (int l = 0; l < L.num_levels; ++l)
             aligned16 = aligned16 && (((uintptr_t)(fwd ? L.feat[l] : (const void*)L.grad[l]) & 15) == 0);
-        if (aligned16 && ((uintptr_t)io & 15) == 0) {
+        if (pool_wants_vec(out_nhwc, C, aligned16)) {   // 8 channels per lane, several bins in flight
 #define VEC_LAUNCH(TT, BW) hipLaunchKernelGGL((roi_align_vec_kernel<TT, BW>), grid, block, tbl, st, L, rois, (TT*)io, fwd ? levels_out : nullptr, C, ph, pw, sampling_ratio, aligned, bpb, spy, spx)
             if (fwd) { if (dtype == DGX_BF16) VEC_LAUNCH(uint16_t, false); else VEC_LAUNCH(float, false); }
             else { if (dtype == DGX_BF16) VEC_LAUNCH(uint16_t, true); else VEC_LAUNCH(float, true); }
@@ -698,7 +566,7 @@ extern "C" int dgx_mask_crop(const uint8_t* masks, const float* boxes, const int
     (void)M;
     if (R <= 0) return DGX_OK;
     if (!masks || !boxes || !mask_idx || !out || S <= 0) return DGX_ERR_BAD_ARG;
-    const int slices = (S * S + 255) / 256 < 8 ? (S * S + 255) / 256 : 8;
+    const int slices = mask_crop_slices(S);
     hipLaunchKernelGGL(mask_crop_kernel, dim3(R, slices), dim3(256), 0, (hipStream_t)stream, masks, boxes, mask_idx, out, H, W, S);
     DGX_LAUNCH_CHECK();
     return DGX_OK;

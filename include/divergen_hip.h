@@ -127,7 +127,14 @@ int dgx_roi_align_bwd(const void* grad_out, const float* rois, float* grad_feat,
 /* Multi-level ROIPooler in one launch: level assignment floor(4 + log2(sqrt(area)/224 + 1e-8))
  * clamped to [min_level, max_level] (D2/modeling/poolers.py:22-58) followed by ROIAlignV2 on the
  * chosen level.  feats/grad_feats: (host) array of num_levels device pointers; Hs/Ws (host) ints;
- * level l has spatial_scale = 2^-(min_level + l).  levels_out i32 (R) optional (may be NULL). */
+ * level l has spatial_scale = 2^-(min_level + l).
+ * The level rule, exactly: with the fp32 values area = (x2 - x1) * (y2 - y1) and t = sqrtf(area) / 224 + 1e-8f (each operation
+ * rounded once), the level is 4 + floor(log2(t)) found by comparing t with powers of two -- an exact comparison, no logarithm is
+ * evaluated -- then clamped; t <= 0 (or NaN) gives the lowest level.  The reference evaluates floor(4 + log2(t)) in fp32, where
+ * 4 + log2(t) rounds up to the integer for t one or two ulps below a power of two: for such boxes, and only for them, the reference
+ * assigns the level above (sqrt(area) = nextafter(224, 0): level 4 there, level 3 here).  tests/test_host_roi_ref.py pins both.
+ * levels_out i32 (R) optional (may be NULL): levels_out[r] = the level index in [0, num_levels) that box r was pooled from, by
+ * this rule; written by the forward only. */
 int dgx_roi_pooler_fwd(const void* const* feats, const int* Hs, const int* Ws, int num_levels,
                        int min_level, const float* rois, void* out, int32_t* levels_out, int N,
                        int C, int R, int ph, int pw, int sampling_ratio, int out_nhwc, int dtype,
